@@ -13,7 +13,9 @@ sorted copy and the tile kernel reads the atoms through the cell-sorted id list:
 with --scaling strong, a 136/N-cell slab of the one 136^3 box — and exchanges a one-cutoff ghost halo with its two ring
 neighbours over RCCL each step.
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step` and the `config` of what was timed); with --dump-outputs DIR it also writes, after the timed steps, what the last
+timed step handed back (see dump_outputs).  Everything below is measured only with --full:
 * `roofline` is for the dominant kernel of the step (the tile kernel, `k_neighbor` = everything between the cell grid
   and the CNA's to-do kernel: it writes the lists AND the labels), timed with HIP events recorded inside the library on the
   launch stream; its algorithmic bytes are what it must move — 24 B of position read, 4 B count, 12 M B of rows and the 4 B label
@@ -28,6 +30,8 @@ Prints ONE JSON line (rank 0):
   rank 1 of 8 of the SAME box with the exchange in loop-back on this one GPU (the wire is not measured).
 * `cpu_baseline` is the CPU oracle (a parity-checked port of the reference's OpenMP C++, oracle/mdapy_oracle.c) timed on
   this box's host cores on the headline's own input; a thread sweep on that same input picks the thread count.
+* N > 1: `config` gains the ranks' atom and ghost counts and the exchange's own time, and `config.strong` times the ONE
+  --cells^3 box cut into the ranks' slabs as a second loop.
 * `--scaling strong` (N > 1): the ONE --cells^3 box cut into N slabs along x instead of one --cells^3 slab per rank.
 """
 import argparse
@@ -63,9 +67,14 @@ def parse():
     p.add_argument("--cells", type=int, default=136, help="FCC cells per axis per GPU (136 -> 10 061 824 atoms)")
     p.add_argument("--max-neigh", type=int, default=16)
     p.add_argument("--sigma", type=float, default=0.0, help="optional thermal rattle (A) of the lattice")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the max_neigh=None / rattled-lattice timings")
-    p.add_argument("--no-pmc", action="store_true", help="do not take the live rocprofv3 PMC passes for roofline.traffic")
+    p.add_argument("--full", action="store_true",
+                   help="also measure roofline / per-kernel times, the extra inputs and paths, the CPU baseline and (N > 1) the exchange "
+                        "and strong-scaling figures; a plain run times the headline step only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (a fixed, seeded sample of rows)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    p.add_argument("--no-extra", action="store_true", help="--full: skip the max_neigh=None / rattled-lattice timings")
+    p.add_argument("--no-pmc", action="store_true", help="--full: do not take the live rocprofv3 PMC passes for roofline.traffic")
     p.add_argument("--cpu-cells", type=int, default=63, help="cells per axis of the CPU-baseline thread sweep (63 -> 1 000 188 atoms)")
     p.add_argument("--cpu-full-cells", type=int, default=0, help="cells per axis of the CPU-baseline run proper (0: --cells, the headline input)")
     p.add_argument("--scaling", choices=["weak", "strong"], default="weak",
@@ -442,6 +451,37 @@ def launch_ranks(args):
     sys.stdout.flush()
 
 
+DUMP_ROWS = 131072  # sampled atoms of a --dump-outputs: (1 + 1 + 1 + 2 M) float64 per atom, 36.7 MB at M = 16
+DUMP_SEED = 20240917
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs, owned=None):
+    """--dump-outputs DIR: what the last timed step handed back to its caller — neighbor_number (N), cna (N), verlet_list (N x M)
+    and distance_list (N x M) of the (owned) atoms — as DIR/<name>.npy in float64 (the integer arrays converted exactly).  Above
+    DUMP_ROWS atoms, the rows of a fixed sample of DUMP_ROWS atoms, drawn with a fixed seed and kept in ascending order; DIR/atom_index.npy
+    holds the sampled atoms' indices.  The same arguments give the same inputs and the same sample, so two builds compare entry for entry."""
+    import torch
+
+    if owned is not None:
+        outputs = {k: v[owned] for k, v in outputs.items()}
+    n = int(outputs["neighbor_number"].shape[0])
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    arrays = {"atom_index": idx.astype(np.float64)}
+    sel = torch.from_numpy(idx).to(outputs["neighbor_number"].device)
+    for name, t in outputs.items():
+        arrays[name] = t.index_select(0, sel).cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     args = parse()
     if args.pmc_child:
@@ -530,7 +570,7 @@ def main():
         def step():
             pattern.zero_()  # the kernels rely on the caller's pre-zeroing (common_neighbor_analysis.py:128)
             _neighbor.build_neighbor_fcna(x, y, z, *bx, RC, verlet, distl, nn, pattern, 1, fill_pads=True)
-            return nn, pattern, None
+            return nn, pattern, None, verlet, distl
 
         def step_two_calls():  # the same step as the two reference calls one after the other (the headline until round 5)
             pattern.zero_()
@@ -545,12 +585,18 @@ def main():
             # slab the second stream costs more than it hides, 0.355 -> 0.377 ms — profiles/r05_strong.txt, r05_halo_cost.txt)
             dom, v_, d_, nn_, pat_ = neighbor_cna_step(dec, x, y, z, gid, RC, M, next_frame=(x, y, z, gid) if n_local >= (1 << 22) else None,
                                                        reuse_buffers=True)  # (the outputs allocated once, as the single-GPU step has them)
-            return nn_, pat_, dom
+            return nn_, pat_, dom, v_, d_
 
     # the timed region: K steps, the neighbour kernel's range timed live by HIP events on its launch stream; the other
     # ranges (cell grid, CNA) are timed by a second, short loop afterwards so that their event pairs do not sit in the K steps
     elapsed, out, prof = timed(step, args.steps, args.warmup, ranges=2)
-    if world == 1:
+    if args.dump_outputs is not None and rank == 0:
+        nn_d, pat_d, dom_d, v_d, d_d = out
+        dump_outputs(args.dump_outputs, {"neighbor_number": nn_d, "cna": pat_d, "verlet_list": v_d, "distance_list": d_d},
+                     owned=None if dom_d is None else dom_d.owned)
+        del nn_d, pat_d, dom_d, v_d, d_d
+    out = out[:3]
+    if world == 1 and args.full:
         _, _, prof_all = timed(step, min(args.steps, 10), 0, ranges=1)
         for name, rec in prof_all.items():
             prof.setdefault(name, rec)
@@ -559,6 +605,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if shared else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if world > 1 and not args.full:
+        dec._drop_pending()  # (the exchange the last timed step prefetched: waited for, never used)
+    if world > 1 and args.full:
         # what the exchange alone costs (selection + packing + ring + append, nothing overlapped), after the timed region:
         # max over ranks; and every rank's owned / ghost atom counts
         dom_x = dec.exchange_halo(x, y, z, gid, RC, sort=False)  # (picks up the exchange the last timed step prefetched)
@@ -586,7 +635,7 @@ def main():
     if world > 1:
         torch.cuda.synchronize()
         dec.check_halo()  # (a static exchange reports an overflowing message one step late: the last step's here)
-        if not strong and cells % world == 0:
+        if not strong and cells % world == 0 and args.full:
             xs_, ys_, zs_, gs_ = slab_positions(torch, dev, cells, rank, args.sigma, cells_x=cells // world)
             box_s = mp.Box(np.diag([A_CU * cells] * 3))
             dec_s = SlabDecomposition(box_s, rank, world, axis=0)
@@ -648,7 +697,7 @@ def main():
                 res["config"]["strong"] = strong_extra
             res["config"]["exchange_note"] = ("exchange_ms: the halo exchange alone, nothing overlapped, max over ranks; inside the timed "
                                               "steps the next step's exchange travels on a side stream under this step's kernels")
-        if "k_neighbor" in prof:
+        if "k_neighbor" in prof and args.full:
             cnt, tot = prof["k_neighbor"]
             avg_ms = tot / cnt
             # read x,y,z (24 B) + write nn (4 B) + rows (12 M B) per atom, and the label this kernel writes as well (4 B)
@@ -675,7 +724,7 @@ def main():
             res["kernels_ms"] = {k: v[1] / v[0] for k, v in prof.items()}
             res["kernels_ms_note"] = ("k_neighbor: HIP events inside the timed steps; the other ranges: a second loop of "
                                       f"{min(args.steps, 10)} steps after them (an event pair costs ~8 us of stream time per range and step)")
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             extra = {}
             # (0) the headline step as the two calls it was until round 5: mdh_build_neighbor, then mdh_fcna — with the plain neighbour
             # kernel's own roofline figure ((28 + 12 M) B per atom), the number the earlier rounds' lines carry
@@ -910,7 +959,7 @@ def main():
             except Exception as e:
                 extra["reference_notebook_calls"] = {"error": f"{type(e).__name__}: {e}"}
             res["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(res))
     if world > 1:

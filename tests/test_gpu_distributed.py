@@ -248,7 +248,7 @@ def test_bench_runs_its_multi_rank_path():
 
     env = dict(os.environ, MDH_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--cells", "40"]
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--cells", "40", "--full"]
     run = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -274,7 +274,7 @@ def test_bench_starts_its_own_ranks():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MDH_BENCH_SHARED_GPU"] = "1"
-    run = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--cells", "40"], cwd=ROOT, env=env,
+    run = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--cells", "40", "--full"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, (run.stdout + run.stderr)[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]

@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 cd $R
 O=gpurun_out
-timeout 900 python bench.py > $O/r03_bench.json 2> $O/r03_bench.err; tail -c 600 $O/r03_bench.json
+timeout 900 python bench.py --full > $O/r03_bench.json 2> $O/r03_bench.err; tail -c 600 $O/r03_bench.json
 mkdir -p $O/r03_prof_bench && (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/r03_prof_bench -o b -- python $R/bench.py --no-extra --no-pmc --no-cpu-baseline > $R/$O/r03_prof_bench/run.log 2>&1)
 PROBE="python $R/tools/nb_probe.py 136 16 0.854 0 2"
 tools/pmc_any.sh nb_sq1 "SQ_WAVES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" $PROBE | tail -2

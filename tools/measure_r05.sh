@@ -22,10 +22,10 @@ two_calls)  # the same step as the two calls it was until the labels moved into 
 fused_ab)   # one call against two on lattices rattled by 0 ... 0.3 A, and against the double-precision form (make fcna64)
   WITH_F64=1 SIGMAS="0.0 0.05 0.1 0.2 0.3" bash tools/ab_fused.sh 2>&1 | tee $O/r05_fused_ab.txt ;;
 bench)     # the default bench line, then the same command under the kernel trace
-  timeout 1200 python bench.py > $O/r05_bench.json 2> $O/r05_bench.err; tail -c 900 $O/r05_bench.json
+  timeout 1200 python bench.py --full > $O/r05_bench.json 2> $O/r05_bench.err; tail -c 900 $O/r05_bench.json
   prof bench python $R/bench.py --no-extra --no-pmc --no-cpu-baseline ;;
 bench_quick)
-  timeout 900 python bench.py --no-cpu-baseline --no-pmc > $O/r05_bench_quick.json 2> $O/r05_bench_quick.err; python - <<P
+  timeout 900 python bench.py --full --no-cpu-baseline --no-pmc > $O/r05_bench_quick.json 2> $O/r05_bench_quick.err; python - <<P
 import json
 r = json.loads(open("$O/r05_bench_quick.json").read().strip().splitlines()[-1])
 print({k: r[k] for k in ("value", "ms_per_step")}, r["roofline"]["frac"], r["kernels_ms"])

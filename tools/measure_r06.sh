@@ -24,7 +24,7 @@ analyses_counters)   # SQ / traffic counters of the same command, four separate 
   tools/pmc_any.sh r06_an_fetch "FETCH_SIZE" $PROBE | tail -1
   tools/pmc_any.sh r06_an_write "WRITE_SIZE" $PROBE | tail -1 ;;
 bench)     # the default bench line, then the same command under the kernel trace
-  timeout 1500 python bench.py > $O/r06_bench.json 2> $O/r06_bench.err; tail -c 600 $O/r06_bench.json
+  timeout 1500 python bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err; tail -c 600 $O/r06_bench.json
   prof bench python $R/bench.py --no-extra --no-pmc --no-cpu-baseline ;;
 counters)   # SQ / traffic counters of the headline step's kernels
   PROBE="python $R/tools/order_probe.py lattice 136 5"
