@@ -283,6 +283,10 @@ __device__ __forceinline__ CnaCounts cna_counts_words(const unsigned (&adj)[NN],
     // key = ncn + 32 nb — (4,2,x) 68, (5,5,5) 165, (4,4,4) 132, (6,6,6) 198 — instead of a chain of compared-and-branched
     // increments (thirty instructions per bond, half of this function, before)
     unsigned packed = 0;
+    // 0xffff in a VGPR: held in an SGPR (the compiler's choice for a constant) it put every mask's v_bfi_b32 in the slower issue class
+    // of instructions that read an SGPR (docs/NOTEBOOK.md "Micro-benchmarks")
+    unsigned lo16 = 0xffffu;
+    asm("" : "+v"(lo16));
 #pragma unroll
     for (int ni = 0; ni < NN; ++ni) {
         if (MAXO < NN && (packed >> 20) > (unsigned)MAXO)
@@ -293,9 +297,9 @@ __device__ __forceinline__ CnaCounts cna_counts_words(const unsigned (&adj)[NN],
         unsigned twice = 0, touched = 0;
 #pragma unroll
         for (int k = 0; k < NW; ++k) {
-            const unsigned lo = (unsigned)(((int)(common << (31 - 2 * k))) >> 31) & 0xffffu;         // row 2k is a common neighbour
-            const unsigned hi = (unsigned)(((int)(common << (30 - 2 * k))) >> 31) & 0xffff0000u;     // row 2k+1
-            const unsigned xk = P[k] & c2 & (lo | hi);
+            const unsigned lo = (unsigned)(((int)(common << (31 - 2 * k))) >> 31); // all ones: row 2k is a common neighbour
+            const unsigned hi = (unsigned)(((int)(common << (30 - 2 * k))) >> 31); // row 2k+1
+            const unsigned xk = P[k] & c2 & ((lo & lo16) | (hi & ~lo16));          // (one v_bfi_b32, every operand a VGPR)
             twice += __popc(xk);
             touched |= xk;
         }
@@ -410,6 +414,169 @@ __device__ __forceinline__ void pair_tests_f32(const float (&ux)[NV], const floa
             : [xc] "v"(ux[c]), [xa] "v"(ux[a]), [yc] "v"(uy[c]), [ya] "v"(uy[a]), [zc] "v"(uz[c]), [za] "v"(uz[a]), [negc] "v"(negc),
               [sc] "n"(c), [sa] "n"(a));
     }
+}
+
+// The same pair tests with each sign SHIFTED into the two bond rows by one v_alignbit_b32 per row (row = row << 1 | e >> 31), as the
+// scan builds its hit masks: 8.5 register-only instructions per pair instead of 9.5.  Row a receives its bits in increasing partner
+// order — the pairs (b, a), b < a, all come before (a, a + 1) in the enumeration — so one extra shift before its first pair (a, a + 1)
+// (and after the last pair, for row NN - 1) leaves the self slot empty, and partner p ends at bit NN - 1 - p: the rows come out
+// BIT-REVERSED.  Read in reverse order as well, r[i] = adj[NN - 1 - i], they are the bond matrix of the same neighbours numbered
+// NN - 1 - p (bit j of r[i] <=> bond between neighbours NN - 1 - i and NN - 1 - j): symmetric, an empty diagonal, and every CNA
+// signature and label is independent of how the neighbours are numbered.
+template <int NN, int NV, int P>
+__device__ __forceinline__ void pair_tests_f32_rev(const float (&ux)[NV], const float (&uy)[NV], const float (&uz)[NV], float negc,
+                                                   unsigned (&adj)[NN], unsigned &w)
+{
+    constexpr int NP = NN * (NN - 1) / 2;
+    if constexpr (P + 1 < NP) {
+        constexpr int a0 = pair_a<NN>(P), c0 = pair_c<NN>(P), a1 = pair_a<NN>(P + 1), c1 = pair_c<NN>(P + 1);
+        if constexpr (a0 > 0 && c0 == a0 + 1) adj[a0] <<= 1; // the self slot of row a0
+        if constexpr (a1 > 0 && c1 == a1 + 1) adj[a1] <<= 1;
+        float t0, t1, t2, s0, s1, s2;
+        // (as in pair_tests_f32: a row that both pairs touch is ONE operand of the block, its two bits shifted in pair order)
+#define MDH_PAIR2_HEAD                                                                                                                 \
+            "v_sub_f32 %[t0], %[xc], %[xa]\n\t"                                                                                        \
+            "v_sub_f32 %[t1], %[yc], %[ya]\n\t"                                                                                        \
+            "v_sub_f32 %[t2], %[zc], %[za]\n\t"                                                                                        \
+            "v_sub_f32 %[s0], %[xd], %[xb]\n\t"                                                                                        \
+            "v_sub_f32 %[s1], %[yd], %[yb]\n\t"                                                                                        \
+            "v_sub_f32 %[s2], %[zd], %[zb]\n\t"                                                                                        \
+            "v_fma_f32 %[t0], %[t0], %[t0], %[negc]\n\t"                                                                               \
+            "v_fma_f32 %[s0], %[s0], %[s0], %[negc]\n\t"                                                                               \
+            "v_fmac_f32 %[t0], %[t1], %[t1]\n\t"                                                                                       \
+            "v_fmac_f32 %[s0], %[s1], %[s1]\n\t"                                                                                       \
+            "v_fmac_f32 %[t0], %[t2], %[t2]\n\t"                                                                                       \
+            "v_fmac_f32 %[s0], %[s2], %[s2]\n\t"                                                                                       \
+            "v_min3_u32 %[w], %[w], %[t0], %[s0]\n\t"
+#define MDH_PAIR2_IN                                                                                                                   \
+            [xc] "v"(ux[c0]), [xa] "v"(ux[a0]), [yc] "v"(uy[c0]), [ya] "v"(uy[a0]), [zc] "v"(uz[c0]), [za] "v"(uz[a0]),                 \
+            [xd] "v"(ux[c1]), [xb] "v"(ux[a1]), [yd] "v"(uy[c1]), [yb] "v"(uy[a1]), [zd] "v"(uz[c1]), [zb] "v"(uz[a1]),                 \
+            [negc] "v"(negc)
+        if constexpr (a0 == a1) {
+            asm(MDH_PAIR2_HEAD
+                "v_alignbit_b32 %[ra], %[ra], %[t0], 31\n\t"
+                "v_alignbit_b32 %[rc], %[rc], %[t0], 31\n\t"
+                "v_alignbit_b32 %[ra], %[ra], %[s0], 31\n\t"
+                "v_alignbit_b32 %[rd], %[rd], %[s0], 31"
+                : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [s0] "=&v"(s0), [s1] "=&v"(s1), [s2] "=&v"(s2), [w] "+v"(w),
+                  [ra] "+v"(adj[a0]), [rc] "+v"(adj[c0]), [rd] "+v"(adj[c1])
+                : MDH_PAIR2_IN);
+        } else if constexpr (c0 == c1) {
+            asm(MDH_PAIR2_HEAD
+                "v_alignbit_b32 %[ra], %[ra], %[t0], 31\n\t"
+                "v_alignbit_b32 %[rc], %[rc], %[t0], 31\n\t"
+                "v_alignbit_b32 %[rb], %[rb], %[s0], 31\n\t"
+                "v_alignbit_b32 %[rc], %[rc], %[s0], 31"
+                : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [s0] "=&v"(s0), [s1] "=&v"(s1), [s2] "=&v"(s2), [w] "+v"(w),
+                  [ra] "+v"(adj[a0]), [rc] "+v"(adj[c0]), [rb] "+v"(adj[a1])
+                : MDH_PAIR2_IN);
+        } else {
+            static_assert(a0 != c1 && c0 != a1, "two pairs of a block share a row that the block binds twice");
+            asm(MDH_PAIR2_HEAD
+                "v_alignbit_b32 %[ra], %[ra], %[t0], 31\n\t"
+                "v_alignbit_b32 %[rc], %[rc], %[t0], 31\n\t"
+                "v_alignbit_b32 %[rb], %[rb], %[s0], 31\n\t"
+                "v_alignbit_b32 %[rd], %[rd], %[s0], 31"
+                : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [s0] "=&v"(s0), [s1] "=&v"(s1), [s2] "=&v"(s2), [w] "+v"(w),
+                  [ra] "+v"(adj[a0]), [rc] "+v"(adj[c0]), [rb] "+v"(adj[a1]), [rd] "+v"(adj[c1])
+                : MDH_PAIR2_IN);
+        }
+#undef MDH_PAIR2_HEAD
+#undef MDH_PAIR2_IN
+        pair_tests_f32_rev<NN, NV, P + 2>(ux, uy, uz, negc, adj, w);
+    } else {
+        if constexpr (P < NP) {
+            constexpr int a = pair_a<NN>(P), c = pair_c<NN>(P);
+            if constexpr (a > 0 && c == a + 1) adj[a] <<= 1;
+            float t0, t1, t2;
+            asm("v_sub_f32 %[t0], %[xc], %[xa]\n\t"
+                "v_sub_f32 %[t1], %[yc], %[ya]\n\t"
+                "v_sub_f32 %[t2], %[zc], %[za]\n\t"
+                "v_fma_f32 %[t0], %[t0], %[t0], %[negc]\n\t"
+                "v_fmac_f32 %[t0], %[t1], %[t1]\n\t"
+                "v_fmac_f32 %[t0], %[t2], %[t2]\n\t"
+                "v_min_u32 %[w], %[w], %[t0]\n\t"
+                "v_alignbit_b32 %[ra], %[ra], %[t0], 31\n\t"
+                "v_alignbit_b32 %[rc], %[rc], %[t0], 31"
+                : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [w] "+v"(w), [ra] "+v"(adj[a]), [rc] "+v"(adj[c])
+                : [xc] "v"(ux[c]), [xa] "v"(ux[a]), [yc] "v"(uy[c]), [ya] "v"(uy[a]), [zc] "v"(uz[c]), [za] "v"(uz[a]), [negc] "v"(negc));
+        }
+        adj[NN - 1] <<= 1; // the self slot of the last row, after its last bit
+    }
+}
+
+// fcc certificate (the fast path in front of the signatures; NN = 12, rows r[] symmetric with an empty diagonal): the label is 1 — every
+// one of the 12 bonds (4,2,1), cna.cpp:496-503 — if and only if every row has four bits and every bonded pair (a, c) has exactly one
+// common neighbour, popc(r[a] & r[c]) == 1.
+//   => the four common neighbours of a bond a form its pool; each of them, c, has exactly one bonded partner inside the pool (that is
+//      popc(r[a] & r[c]) == 1), so the pool's bonds are a perfect matching of four atoms: nb = 2 bonds that share no atom, chain = 1.
+//   <= a (4,2,1) pool is two disjoint bonds on four atoms: every pool atom has exactly one partner in it.
+// (A cuboctahedron passes; hcp's (4,2,2) bonds — two bonds that share an atom, and an atom left alone — fail it.)  Per pair, register
+// only: m = the bond bit of (a, c) as a mask (v_bfe_i32), x = r[a] & r[c] & m (v_bitop3), u = popc(x) + m (v_bcnt with m as its addend:
+// popc - 1 for a bond, 0 for a non-bond), OR-ed into one word — four instructions; per row popc(r) - 4.
+template <int NN>
+__device__ __forceinline__ bool fcc_certificate(const unsigned (&r)[NN])
+{
+    unsigned bad = 0;
+#pragma unroll
+    for (int a = 0; a < NN; ++a)
+        bad |= (unsigned)__popc(r[a]) - 4u;
+    // (each pair one asm block, chained through `bad`: written in C the compiler hoisted the pairs' masks and counts ahead of the
+    // chain and the kernel spilled registers to scratch memory)
+#pragma unroll
+    for (int a = 0; a < NN; ++a)
+#pragma unroll
+        for (int c = a + 1; c < NN; ++c) {
+            unsigned m, x;
+            asm("v_bfe_i32 %[m], %[ra], %[c], 1\n\t"
+                "v_bitop3_b32 %[x], %[ra], %[rc], %[m] bitop3:0x80\n\t" // r[a] & r[c] & m
+                "v_bcnt_u32_b32 %[x], %[x], %[m]\n\t"
+                "v_or_b32 %[bad], %[bad], %[x]"
+                : [m] "=&v"(m), [x] "=&v"(x), [bad] "+v"(bad)
+                : [ra] "v"(r[a]), [rc] "v"(r[c]), [c] "n"(c));
+        }
+    return bad == 0u;
+}
+
+// The fixed-cutoff label of a 12-neighbour atom from the pairs instead of the bonds (the general path behind fcc_certificate; the same
+// label as fcna_label_words<12>).  With twelve rows only labels 1, 2 and 4 are possible (label 3 asks for 8 + 6 signatures), and they
+// ask for every row to be (4,2,x) or every row (5,5,5).  For the bond centre--a: ncn = popc(r[a]); 2 nb = the sum over its common
+// neighbours c of popc(r[a] & r[c]) — each bonded pair's x = r[a] & r[c] (masked by the bond bit as above) is counted in BOTH rows —
+// and the atoms the pool's bonds touch are the OR of those x.  Two bonds on four atoms touch three (chain 2: (4,2,2)) or four
+// ((4,2,1)), so once every row is (4,2,x) the touched counts add up to 48 - (number of (4,2,2) rows): 48 is fcc, 42 hcp.  (5,5,x) is
+// (5,5,5) whatever x (signature(): five bonds on the five atoms of the pool are one cluster).  One register per row: 2 nb in the low
+// half (v_bcnt with the row as its addend), the touched atoms in the high half (v_lshl_or): six register-only instructions per pair.
+template <int NN>
+__device__ __forceinline__ int fcna_label_pairs(const unsigned (&r)[NN])
+{
+    static_assert(NN == 12, "fcna_label_pairs decides the labels of 12-neighbour atoms only");
+    unsigned acc[NN];
+#pragma unroll
+    for (int a = 0; a < NN; ++a) acc[a] = 0;
+#pragma unroll
+    for (int a = 0; a < NN; ++a)
+#pragma unroll
+        for (int c = a + 1; c < NN; ++c) {
+            unsigned m, x; // (one asm block per pair, as in fcc_certificate)
+            asm("v_bfe_i32 %[m], %[ra], %[c], 1\n\t"
+                "v_bitop3_b32 %[x], %[ra], %[rc], %[m] bitop3:0x80\n\t" // r[a] & r[c] & m
+                "v_bcnt_u32_b32 %[aa], %[x], %[aa]\n\t"
+                "v_bcnt_u32_b32 %[ac], %[x], %[ac]\n\t"
+                "v_lshl_or_b32 %[aa], %[x], 16, %[aa]\n\t"
+                "v_lshl_or_b32 %[ac], %[x], 16, %[ac]"
+                : [m] "=&v"(m), [x] "=&v"(x), [aa] "+v"(acc[a]), [ac] "+v"(acc[c])
+                : [ra] "v"(r[a]), [rc] "v"(r[c]), [c] "n"(c));
+        }
+    unsigned bad4 = 0, bad5 = 0, sum_touched = 0;
+#pragma unroll
+    for (int a = 0; a < NN; ++a) {
+        const unsigned key = (unsigned)__popc(r[a]) + ((acc[a] & 0xffffu) << 4); // ncn + 16 (2 nb), as in cna_counts_words
+        bad4 |= key ^ 68u;                                                        // (4,2,x)
+        bad5 |= key ^ 165u;                                                       // (5,5,x)
+        sum_touched += (unsigned)__popc(acc[a] >> 16);
+    }
+    if (bad4 == 0u) return sum_touched == 48u ? 1 : (sum_touched == 42u ? 2 : 0); // cna.cpp:496-503
+    return bad5 == 0u ? 4 : 0;
 }
 
 // to-do list of atoms left to a later kernel: todo[0] = count, todo[1..] = atom ids

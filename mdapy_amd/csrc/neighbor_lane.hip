@@ -356,10 +356,21 @@ __device__ __forceinline__ int lane_fcna_f32(Index index_of, const float4 *__res
     for (int a = 0; a < NN; ++a)
         adj[a] = 0;
     unsigned w = 0x7f7fffffu; // bits of the smallest non-negative d2 - c seen
-    pair_tests_f32<NN, NN, 0>(ux, uy, uz, negc, adj, w);
+    pair_tests_f32_rev<NN, NN, 0>(ux, uy, uz, negc, adj, w); // (rows bit-reversed: read in reverse order below)
+    unsigned r[NN];
+#pragma unroll
+    for (int a = 0; a < NN; ++a)
+        r[a] = adj[NN - 1 - a];
     if (w <= __float_as_uint(W))
         return -1;
-    return fcna_label_words<NN, RowsReg<NN>>(adj, RowsReg<NN>(adj)); // (the label fetches no row by a computed index: cna_counts_words)
+    if constexpr (NN == 12) {
+        // fcc certificate first (four instructions per pair): a perfect or mildly rattled fcc lattice labels every lane here and
+        // the wave skips the signatures; the lanes it does not certify count them from the pairs (fcna_label_pairs: the same label)
+        if (fcc_certificate<NN>(r))
+            return 1;
+        return fcna_label_pairs<NN>(r);
+    }
+    return fcna_label_words<NN, RowsReg<NN>>(r, RowsReg<NN>(r)); // (the label fetches no row by a computed index: cna_counts_words)
 }
 
 // 4 x 4 transpose of 16-byte pieces among the four lanes of a quad: lane u's piece v <-> lane v's piece u.  Two butterfly
