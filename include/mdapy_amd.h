@@ -116,14 +116,16 @@ int mdh_debug_set_rdf_variant(int variant);
 /* k nearest neighbours: 0 = the near kernel (sorted list in registers, 27 cells) followed by the general kernel on the queries it
  * lists; 1 = the general kernel for every query (A/B measurements, tests; results identical) */
 int mdh_debug_set_knn_variant(int variant);
-/* test hook: 0 = per-degree register-resident stage 1 of the Steinhardt parameters where compiled (default), 1 = generic kernel */
+/* test hook: 0 = per-degree register-resident stage 1 of the Steinhardt parameters where compiled (default), 1 = generic kernel;
+ * any other value returns MDH_ERR_ARG */
 int mdh_debug_set_sq_variant(int variant);
 /* test hook: structure entropy, 0 = the ladder kernel where it applies (<= 40 bins, rc^2 / 2 sigma^2 <= 640) with the lane count
  * picked by the row width (default), 1 = the direct kernel (an exponential per term), 2 / 3 / 4 / 5 = the ladder with 1 / 2 / 4 / 8
  * lanes to a row */
 int mdh_debug_set_entropy_variant(int variant);
 /* test hook: vertex capacity of the first pass of the PTM neighbour ordering (10 default, 15; 5 sends most atoms through
- * the second, 28-vertex pass, whose results must be the same) */
+ * the second, 28-vertex pass, whose results must be the same).  0 = automatic; a negative value selects the polygons in space
+ * instead of in their plane's coordinates; 100 and above return MDH_ERR_ARG */
 int mdh_debug_set_ptm_order_cap(int cap);
 /* test hook: out4[k] = smallest double d with floor(d/L + 0.5) >= k-1 (k = 0..3) for a periodic orthogonal
  * axis of length L — the exact decision points that let the kernels replace floor(d/L+0.5) by compares. */

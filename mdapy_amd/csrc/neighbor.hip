@@ -778,16 +778,15 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
         hipLaunchKernelGGL(k_order_far_flag, dim3(1), dim3(1024), 0, st, x, y, z, N, b, nb[0], nb[1], nb[2], rec_flag);
     }
     const unsigned gen = next_scan_gen(); // stamps of this build's k_assign; the (first) scan below is launched with the same value
-    // atoms per lane (A/B: MDH_ASSIGN_K = 1, 2, 4; small systems keep one atom per lane: they need the workgroups to fill the chip)
-    static const int assign_k_env = [] { const char *e = std::getenv("MDH_ASSIGN_K"); return e ? std::atoi(e) : 0; }();
+    // atoms per lane: four; small systems keep one atom per lane (they need the workgroups to fill the chip)
     // (measured at 10 M atoms: 145 -> 120 us on a lattice, 162 -> 162 on a polycrystal — 10 M runs of one atom, the atomics' own
     // throughput — 413 -> 440 on a shuffled frame, which therefore keeps one: profiles/r05_assign_k.txt)
-    const int assign_k = assign_k_env > 0 ? assign_k_env : ((N >= (int64_t)1 << 20 && !scattered) ? 4 : 1);
+    const bool assign4 = N >= (int64_t)1 << 20 && !scattered;
 #define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)wrap_first, cell_id, rank, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
     if (b.tri) {
-        if (assign_k >= 4) MDH_ASSIGN(true, 4); else if (assign_k >= 2) MDH_ASSIGN(true, 2); else MDH_ASSIGN(true, 1);
+        if (assign4) MDH_ASSIGN(true, 4); else MDH_ASSIGN(true, 1);
     } else {
-        if (assign_k >= 4) MDH_ASSIGN(false, 4); else if (assign_k >= 2) MDH_ASSIGN(false, 2); else MDH_ASSIGN(false, 1);
+        if (assign4) MDH_ASSIGN(false, 4); else MDH_ASSIGN(false, 1);
     }
 #undef MDH_ASSIGN
     auto scan_piece = [&](int64_t from, int64_t to, unsigned use_gen, int *flags) {
@@ -1532,8 +1531,7 @@ int neighbor_rows_device(Scope &sc, const double *dx, const double *dy, const do
     MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, dkey, true));
     // pads written (the tile kernel then stores whole 16-byte groups; leaving the pads out measured SLOWER: 2.96 against 2.54 ms
     // at 10 M atoms, rc 3.8, 24 slots); distances wanted or not (rows of more than 16 slots: the wide instance skips them)
-    static const bool want_dist = [] { const char *e = std::getenv("MDH_KNN_ROWS_DIST"); return e && std::atoi(e) != 0; }(); // A/B
-    lane_ids_only(ids_only && !want_dist);
+    lane_ids_only(ids_only);
     const int rcode = neighbor_pass(sc, cg, b, N, rc, dv, dd, dn, M, 2, nullptr);
     lane_ids_only(false);
     return rcode;

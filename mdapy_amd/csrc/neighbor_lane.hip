@@ -64,9 +64,9 @@
 namespace mdh {
 namespace lane {
 
-// A workgroup is NW waves (template parameter of the kernel): 4 — 256 threads, four workgroups per CU — or 8 for the big-tile
-// instance — 512 threads, two per CU.  A tile has at most one halo cell per thread.
-constexpr int cen_cap(int nw) { return 80 * nw; } // centre atoms a tile may hold
+// A workgroup is NW waves: 256 threads, four workgroups per CU.  A tile has at most one halo cell per thread.
+constexpr int NW = 4;
+constexpr int CEN_CAP = 80 * NW; // centre atoms a tile may hold
 // tickets of a row + the spare slot, rounded up (rows are read back four tickets at a time).  (cna_rows: 28 bytes, room for a centre's
 // bond rows — built, and dropped: the 2 KB cost the headline tile 49 atoms of room, 169 of its 51 200 tiles went to the slice pass
 // (33 us), and since cna_counts_words fetches no row by a computed index nothing needs them)
@@ -122,7 +122,6 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int NW>
 __device__ __forceinline__ int excl_scan_block(int v, int *scratch, int *total)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -306,37 +305,10 @@ __device__ __forceinline__ unsigned scan_run_f64(const double2 *__restrict__ lxy
     return m;
 }
 
-// fixed-cutoff CNA of one centre (FixedCNA, cna.cpp:429-506) from the tile: its NN tickets name the listed neighbours in row
-// order, their RAW positions are staged.  plain: no staged atom of this tile carries an image shift, and
-// two neighbours of one centre are less than 2 rc < L / 2 apart (>= 7 cells per periodic axis): the minimum image of every
-// pair is the plain difference, d - L * 0 == d as the reference computes it.  Tiles at a periodic face classify the spread
-// of the positions as k_fcna does; -1: spread too far (atoms handed in outside the box), the atom goes to the to-do list
-template <bool TRI, int NN, class Index>
-__device__ __forceinline__ int lane_fcna(const DBox &b, Index index_of, const double2 *__restrict__ lxy,
-                                         const double *__restrict__ lz, bool plain, double cut2)
-{
-    double px[NN], py[NN], pz[NN];
-#pragma unroll
-    for (int a = 0; a < NN; ++a) {
-        const int k = index_of(a); // LDS index of the a-th listed neighbour
-        const double2 c = lxy[k];
-        px[a] = c.x; py[a] = c.y; pz[a] = lz[k];
-    }
-    Rows R;
-    if (TRI) {
-        R = bond_rows_reg<true, NN>(b, px, py, pz, cut2);
-    } else {
-        const int cls = plain ? 2 : span_class3<NN>(b, px, py, pz);
-        if (cls == 0)
-            return -1;
-        R = bond_rows_ortho<NN>(b, px, py, pz, cut2, cls == 2);
-    }
-    return fcna_label<NN>(R);
-}
-
-// The same label with the pair tests in SINGLE precision on the tile's staged coordinates (f4: relative to the tile's corner, every
+// fixed-cutoff CNA of one centre (FixedCNA, cna.cpp:429-506) from the tile: its NN tickets name the listed neighbours in row order.
+// The pair tests run in SINGLE precision on the tile's staged coordinates (f4: relative to the tile's corner, every
 // staged atom already in the image the tile sees — a difference of two of them IS the minimum image while the box is at least
-// seven cells wide, which the tile kernel asks for anyway): no second read of the positions, 36 registers instead of 72, ten
+// seven cells wide, which the tile kernel asks for anyway): no second read of the positions, 36 registers instead of the 72 of double-precision ones, ten
 // register-only instructions per pair (cna.hip fcna_atom_f32).  The decision band is the scan's own: both tests compare a squared
 // distance of two staged atoms with rc^2 (neighbor.cpp:160 and cna.cpp:459-466 use the same `<=`), and the bound behind (negc, W)
 // holds for any two atoms of the 3 x 3 x 3 cells around a centre.  -1: a pair inside the band — the atom goes on the to-do list and
@@ -441,22 +413,13 @@ __device__ __forceinline__ CellGrid::Packed load_record(const CellGrid::Packed *
 // 1.15 against 1.23 ms on the headline build — the loop-carried state costs scalar-register spills in every phase)
 // FCNA: the fixed-cutoff CNA label of every centre as well (mdh_build_neighbor_fcna)
 // TK8 (rows of at most 16 slots): one-byte tickets, no row-word / wrapped-centre tables, rows written by the centre's own lane,
-// and (without the fused CNA) the kernel held to 128 VGPRs: a workgroup then needs under 40 KB of LDS and FOUR share a CU.
-// false: two-byte tickets and the slot-per-lane write-out (rows of up to 64 slots)
-// NW: waves per workgroup.  4: tiles of up to 256 halo cells, four workgroups per CU.  8 (one-byte instance without the fused CNA
-// only): tiles of up to 512 halo cells, two workgroups per CU — the same sixteen waves per CU, but a tile of 6 x 6 x 5 cells
-// stages 2.5 halo cells per centre cell instead of 3.15, its per-wave front phases serve twice the centres, and its ~440 centres
-// fill seven chunks of 64 better than ~196 fill three or four
+// and the kernel held to 128 VGPRs (the fused label's single-precision pair tests fit them): a workgroup then needs under 40 KB of
+// LDS and FOUR share a CU.  false: two-byte tickets and the slot-per-lane write-out (rows of up to 64 slots)
 // IND: the atoms are read through the cell-sorted id list from the caller's arrays (load_record)
-template <bool COUNT, bool TRI, bool LOOP, bool FCNA, bool TK8, int NW = 4, bool IND = false>
-#ifdef MDH_FCNA_F64
-#define MDH_FCNA_LEAN false // the double-precision pair tests of the fused label need ~175 VGPRs: three workgroups per CU
-#else
-#define MDH_FCNA_LEAN true  // the single-precision ones fit the 128 of the plain instance: four
-#endif
 // (the walked instances that also label — the slice pass, a tile list longer than its launch: rare — take the registers they want:
 // held to 128 they spill a dozen to scratch memory, and a launch that reserves scratch is slower to start even when it finds no work)
-__global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP))) ? 16 / NW : 1) void k_neighbor_lane(
+template <bool COUNT, bool TRI, bool LOOP, bool FCNA, bool TK8, bool IND = false>
+__global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) void k_neighbor_lane(
     const CellGrid::Packed *__restrict__ pk, const int *__restrict__ cell_start, DBox b,
     Grid g, double rc, float negc, float W, int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn,
     int M, int write_pads, int cap, int *__restrict__ flags, unsigned char *__restrict__ tile_flag, int nt0,
@@ -468,7 +431,6 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
     const int TXY = ts.txy, TZ = ts.tz;
     const int coded = IND ? flags[4] : 0; // (uniform) some atom was handed in outside the box: the image codes are read as well
     const int HXY = TXY + 2, HZ = TZ + 2, NH = HXY * HXY * HZ;
-    constexpr int CENC = cen_cap(NW);
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -481,7 +443,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
     double2 *lxy = reinterpret_cast<double2 *>(f4 + cap);           // [cap] staged raw x, y
     double *lz = reinterpret_cast<double *>(lxy + cap);             // [cap] staged raw z
     unsigned *cen = reinterpret_cast<unsigned *>(lz + cap);         // [CEN_CAP] centre atoms: LDS index | halo cell << 11
-    unsigned short *lsh = reinterpret_cast<unsigned short *>(cen + CENC); // [cap] combined image code of a staged atom seen from this tile
+    unsigned short *lsh = reinterpret_cast<unsigned short *>(cen + CEN_CAP); // [cap] combined image code of a staged atom seen from this tile
     Ticket *tk = reinterpret_cast<Ticket *>(lsh + cap + (cap & 1)); // [NT][TKS] tickets (slot M swallows the hits past M); wave w owns rows 64 w ...
     const unsigned f4_lds = (unsigned)(unsigned long)(lds_byte *)smem;
     // halo cell: population — needed from the block scan's barrier to the run table only, so it lives in the ticket rows, cell t
@@ -601,10 +563,10 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
         hc(tid) = (unsigned)cnt; // the neighbours in z need it for their run (published by the scan's barrier)
 
         int total2;
-        const int off2 = excl_scan_block<NW>(cnt | (centre_cell ? cnt << 16 : 0), scan_tmp, &total2); // both prefixes in one scan (each < 2^15)
+        const int off2 = excl_scan_block(cnt | (centre_cell ? cnt << 16 : 0), scan_tmp, &total2); // both prefixes in one scan (each < 2^15)
         const int total = total2 & 0xffff, ncentres = total2 >> 16;
         const int off0 = off2 & 0xffff, coff = off2 >> 16;
-        bool ok = !(total > cap || ncentres > CENC); // else: listed for the next pass
+        bool ok = !(total > cap || ncentres > CEN_CAP); // else: listed for the next pass
         const bool no_centres = ncentres == 0;          // (uniform) a tile of ghost planes only: nothing to stage, nothing to list
         if (no_centres) ok = false;
         STAMP(2);
@@ -671,11 +633,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                         if (!TRI && edge)
                             far = far || !(ux >= flo && ux <= fhx && uy >= flo && uy <= fhx && uz >= flo && uz <= fhz);
                         const int p = off0 + k + v;
-#ifdef MDH_EXP_GATHER // measuring build (make gather): the staged atom carries its record's index, not its id
-                        f4[p] = make_float4(ux, uy, uz, __int_as_float(src + k + v));
-#else
                         f4[p] = make_float4(ux, uy, uz, __int_as_float(d[v]));
-#endif
                         lxy[p] = make_double2(a[v], bb[v]);
                         lz[p] = c[v];
                         lsh[p] = (unsigned short)code;
@@ -837,11 +795,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                 int hits = 0;
 #pragma unroll
                 for (int r = 0; r < 9; ++r) hits += __builtin_popcount(mk[r]) + (WIDE ? __builtin_popcount(mk2[r]) + __builtin_popcount(mk3[r]) : 0);
-#ifdef MDH_EXP_GATHER
-                id = pk[__float_as_int(s.w)].id;
-#else
                 id = __float_as_int(s.w);
-#endif
                 nn[id] = hits; // keeps counting past M (neighbor.cpp:172-177)
                 if (COUNT) {
                     vmax = max(vmax, hits);
@@ -891,13 +845,8 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                             return (int)(hr[run_cell(cb, r)] & 0xffffu) + (int)(t & ((1u << JB) - 1u));
                         };
                         int label = 0;
-#ifdef MDH_FCNA_F64 // measuring build (make fcna64): the pair tests in double precision on the raw coordinates, as until round 5
-                        if (hits == 12 && M >= 12) label = lane_fcna<TRI, 12>(b, index_of, lxy, lz, !general_tile, rcsq);
-                        else if (hits == 14 && M >= 14) label = lane_fcna<TRI, 14>(b, index_of, lxy, lz, !general_tile, rcsq);
-#else
                         if (hits == 12 && M >= 12) label = lane_fcna_f32<12>(index_of, f4, negc, W);
                         else if (hits == 14 && M >= 14) label = lane_fcna_f32<14>(index_of, f4, negc, W);
-#endif
                         if (label > 0) pattern[id] = label;
                         else if (label < 0) defer(cna_todo, id);
                     }
@@ -945,19 +894,6 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                         double2 cj[4];
                         double zj[4], d2[4];
                         int nid[4], sh[4];
-#ifdef MDH_EXP_GATHER // the hits' raw doubles through L2 in one batched gather per group of four
-                        int qx[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) qx[u] = mine ? __float_as_int(f4[k[u]].w) : 0; // (a lane without a centre reads whatever LDS holds)
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const CellGrid::Packed rj = pk[qx[u]];
-                            cj[u] = make_double2(rj.x, rj.y);
-                            zj[u] = rj.z;
-                            nid[u] = rj.id;
-                            sh[u] = (!TRI && general_tile) ? (int)lsh[k[u]] : 0;
-                        }
-#else
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             cj[u] = lxy[k[u]];
@@ -965,7 +901,6 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                             nid[u] = __float_as_int(f4[k[u]].w);
                             sh[u] = (!TRI && general_tile) ? (int)lsh[k[u]] : 0;
                         }
-#endif
                         bool slow = false;
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
@@ -996,22 +931,6 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                 // of the CU, at about two cycles per request, was a quarter of the kernel's time.
                 {
                     const int rid = mine ? id : -1;
-#ifdef MDH_EXP_SCATTER // measuring build (make scatter): every lane stores its own row, 16 bytes at a time (64 line requests per store instruction)
-                    if (write_pads && (M & 3) == 0) {
-                        if (rid >= 0) {
-                            const uint64_t row = (uint64_t)(unsigned)id * (unsigned)M;
-#pragma unroll
-                            for (int pp = 0; pp < 4; ++pp)
-                                if (4 * pp < M)
-                                    *reinterpret_cast<Int4 *>(verlet + row + 4 * pp) = Int4{idv[4 * pp], idv[4 * pp + 1], idv[4 * pp + 2], idv[4 * pp + 3]};
-#pragma unroll
-                            for (int piece = 0; piece < 8; ++piece)
-                                if (2 * piece < M)
-                                    *reinterpret_cast<Int4 *>(dist + row + 2 * piece) = Int4{__double2loint(dv[2 * piece]), __double2hiint(dv[2 * piece]),
-                                                                                              __double2loint(dv[2 * piece + 1]), __double2hiint(dv[2 * piece + 1])};
-                        }
-                    } else
-#endif
                     if (write_pads && (M & 3) == 0) {
                         const int odd1 = -(lane & 1), odd2 = -((lane >> 1) & 1), u4 = lane & 3;
                         int P[4][4];
@@ -1101,11 +1020,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || (MDH_FCNA_LEAN && !LOOP)
                         for (int u = 0; u < 4; ++u) {
                             cj[u] = lxy[k[u]];
                             zj[u] = lz[k[u]];
-#ifdef MDH_EXP_GATHER
-                            nid[u] = mine ? pk[__float_as_int(f4[k[u]].w)].id : 0;
-#else
                             nid[u] = __float_as_int(f4[k[u]].w);
-#endif
                             sh[u] = (!TRI && general_tile) ? (int)lsh[k[u]] : 0;
                         }
                         bool slow = false;
@@ -1297,11 +1212,11 @@ int grid_stats_hint(Scope &sc, const CellGrid &cg, int64_t N, GridStats *out)
 namespace lane {
 
 // tk8: one-byte tickets, else two-byte ones; rows of (M + 1) tickets rounded up to a multiple of four; rw rows per wave
-static size_t lds_bytes(int cap, int64_t M, bool tk8, int rw, int nw = 4, bool fcna = false)
+static size_t lds_bytes(int cap, int64_t M, bool tk8, int rw, bool fcna = false)
 {
     const size_t wave = std::max<size_t>((size_t)rw * (size_t)ticket_row((int)M, false) * (tk8 ? 1 : 2), 256); // (the kernel's wstride)
-    const size_t tk = (size_t)nw * wave;
-    return (size_t)cap * 16 + (size_t)cap * 16 + (size_t)cap * 8 + (size_t)cen_cap(nw) * 4 + (size_t)(cap + (cap & 1)) * 2 + ((tk + 15) & ~(size_t)15);
+    const size_t tk = (size_t)NW * wave;
+    return (size_t)cap * 16 + (size_t)cap * 16 + (size_t)cap * 8 + (size_t)CEN_CAP * 4 + (size_t)(cap + (cap & 1)) * 2 + ((tk + 15) & ~(size_t)15);
 }
 
 } // namespace lane
@@ -1369,74 +1284,43 @@ static LanePlan plan_lane_fresh(const DBox &b, const Grid &g, int64_t N, int64_t
     // 8.8 -> 5.7 ms), behind beyond (rc 6.5 A, 24 atoms per cell: a third of the tiles hold a run of more than 96 candidates and
     // go to the mop-up code, 10.9 -> 12.7 ms)
     if (M > 64 && pop > 19.5) { g_last_plan[6] = -7; g_last_plan[5] = (int)(1000.0 * pop); return p; }
-    static const int cap_env = [] { const char *e = std::getenv("MDH_LANE_CAP"); return e ? std::atoi(e) : 0; }();
-    static const int wgs_env = [] { const char *e = std::getenv("MDH_LANE_WGS"); return e ? std::atoi(e) : 0; }(); // A/B: workgroups per CU the LDS is cut for
     // rows of at most 16 slots in cells of a few atoms: one-byte tickets, the lean LDS layout, rows written by the centre's lane;
-    // four workgroups per CU where the instance keeps to 128 VGPRs (not the fused CNA)
-    static const int tk8_env = [] { const char *e = std::getenv("MDH_LANE_TK8"); return e ? std::atoi(e) : 1; }(); // A/B: 0 = the slot-per-lane write-out always
-    const bool tk8 = (count && !long_runs) || (tk8_env && M <= 16 && !long_runs);
-    const int max_wgs = (tk8 && (!fcna || MDH_FCNA_LEAN)) ? 4 : 3;
+    // four workgroups per CU where the instance keeps to 128 VGPRs
+    const bool tk8 = (count || M <= 16) && !long_runs;
+    const int max_wgs = tk8 ? 4 : 3;
     // LDS budget: four workgroups per CU (the 128-VGPR instance only), else three, two, one, if the tile that allows is not
     // much worse than what fewer would get.  Rows of many slots in cells of many atoms (rc = 5 A, 50 slots: the reference's
     // own benchmark call) leave few centres per tile: the ticket rows are sized for them (rw rows per wave), not for 64.
-    // eight waves per workgroup (tiles of up to 512 halo cells, two workgroups per CU): the one-byte instance without the fused
-    // CNA, where four workgroups of four waves would share the CU anyway
-#ifdef MDH_LANE_NW8
-    static const int nw_env = [] { const char *e = std::getenv("MDH_LANE_NW"); return e ? std::atoi(e) : 0; }(); // A/B: 4 or 8
-#else
-    constexpr int nw_env = 0;
-#endif
-    // A/B (tools/measure_r05.sh lane_tiles): MDH_LANE_TILE="txy,tz" forces the tile shape where it fits
-    static const int tile_env = [] { const char *e = std::getenv("MDH_LANE_TILE"); int a = 0, c = 0; return (e && std::sscanf(e, "%d,%d", &a, &c) == 2) ? a * 100 + c : 0; }();
     Shape best{0, 0};
-    int best_cap = 0, best_wgs = 0, best_rw = 64, best_nw = 4;
+    int best_cap = 0, best_wgs = 0, best_rw = 64;
     double best_score = -1.0;
-    bool stop = false;
-    for (int nw = 8; nw >= 4 && !stop; nw -= 4)
-    for (int wgs = (nw == 8 ? 2 : max_wgs); wgs >= 1; --wgs) {
-        if (nw == 8 && (!(tk8 && !fcna) || nw_env != 8 || wgs < 2)) // measured 3 % slower than four waves: on request only
-            continue;
-        if (nw == 4 && nw_env == 8 && tk8 && !fcna)
-            continue;
-        if (wgs_env > 0 && nw == 4 && wgs != std::min(wgs_env, max_wgs))
-            continue;
-        const int nthr = nw * 64;
+    const int nthr = NW * 64;
+    for (int wgs = max_wgs; wgs >= 1; --wgs) {
         // static tables (1.1 KB: the run table, scan scratch, flags) and a margin.  LDS is handed out in 512-byte granules: 40 960 B
         // in all give four workgroups per CU (measured: 40 544 do, 41 216 do not; 52.9 KB three, 54.3 KB not)
-        const long budget = nw == 8 ? 160 * 1024 / 2 - 2112 - 64 : 160 * 1024 / wgs - 1088 - (wgs == 4 ? 64 : 1600);
+        const long budget = 160 * 1024 / wgs - 1088 - (wgs == 4 ? 64 : 1600);
         for (int txy = 1; txy <= 8; ++txy)
             for (int tz = 1; tz <= 24; ++tz) {
                 const int nh = (txy + 2) * (txy + 2) * (tz + 2);
                 if (nh > nthr)
                     continue;
-                if (tile_env && (txy != tile_env / 100 || tz != tile_env % 100))
-                    continue;
                 const int ncc = txy * txy * tz;
                 const double c = ncc * pop;                                 // centre atoms per tile
-                if (c * 1.15 > cen_cap(nw))
+                if (c * 1.15 > CEN_CAP)
                     continue;
                 int rw = 64;
-                if (!tk8) rw = std::min(64, std::max(8, ((int)std::ceil(c * 1.15 / nw) + 3) & ~3)); // (a row is a multiple of eight bytes: any count keeps the waves' blocks aligned)
-                const long fixed = (long)lds_bytes(0, M, tk8, rw, nw, fcna);
-                int cap = (int)((budget - fixed - 2) / 42);
-                if (cap_env > 0) cap = cap_env;
-                cap = std::min(cap, 2040); // (a centre's LDS index takes 11 bits of its table entry)
+                if (!tk8) rw = std::min(64, std::max(8, ((int)std::ceil(c * 1.15 / NW) + 3) & ~3)); // (a row is a multiple of eight bytes: any count keeps the waves' blocks aligned)
+                const long fixed = (long)lds_bytes(0, M, tk8, rw, fcna);
+                const int cap = std::min((int)((budget - fixed - 2) / 42), 2040); // (a centre's LDS index takes 11 bits of its table entry)
                 if (cap < 64 || nh * pop > 0.875 * cap) // head-room for density fluctuations; what overflows goes to the slice pass
                     continue;
-                const double passes = std::ceil(c * 1.15 / (nw * rw)); // (head-room: a second pass for a handful of centres is a waste)
+                const double passes = std::ceil(c * 1.15 / (NW * rw)); // (head-room: a second pass for a handful of centres is a waste)
                 const double util = c / (passes * nthr);                   // lane utilisation of the scan
                 const double reuse = (double)ncc / (double)nh;             // centre cells per staged cell
-                const int wpc = wgs * nw;                                  // waves per CU
+                const int wpc = wgs * NW;                                  // waves per CU
                 const double score = util * (0.35 + reuse) * (wpc == 16 ? 1.1 : (wpc == 12 ? 1.0 : (wpc == 8 ? 0.85 : (M > 64 ? 0.45 : 0.6))));
-                // the big tile must leave the chip full: at least four workgroups' worth of tiles per CU
-                if (nw == 8 && (double)occ / ncc < 4.0 * 256.0)
-                    continue;
-                if (score > best_score) { best_score = score; best = Shape{txy, tz}; best_cap = cap; best_wgs = wgs; best_rw = rw; best_nw = nw; }
+                if (score > best_score) { best_score = score; best = Shape{txy, tz}; best_cap = cap; best_wgs = wgs; best_rw = rw; }
             }
-        if (cap_env > 0) {
-            stop = true;
-            break;
-        }
     }
     if (!best.txy) { g_last_plan[6] = -6; return p; }
     // Decision band of the single-precision scan (file header).  E bounds the staged coordinates (far-atom check of the
@@ -1478,7 +1362,6 @@ static LanePlan plan_lane_fresh(const DBox &b, const Grid &g, int64_t N, int64_t
     p.tk8 = tk8;
     p.wgs = best_wgs;
     p.rw = best_rw;
-    p.nw = best_nw;
     p.occupied = occ;
     p.last_listed = gs.last_listed;
     p.listed_sink = gs.listed_sink;
@@ -1487,8 +1370,8 @@ static LanePlan plan_lane_fresh(const DBox &b, const Grid &g, int64_t N, int64_t
     // per cent of empty blocks (the corner cell of a 100^3-cell fcc box holds no lattice site) cost a workgroup each that finds no
     // centre and leaves; the list costs three launches
     p.full = (double)occ >= 0.98 * (double)g.ncell;
-    g_last_plan[0] = p.txy; g_last_plan[1] = p.tz; g_last_plan[2] = p.cap; g_last_plan[3] = (int)lds_bytes(p.cap, M, tk8, p.rw, p.nw, fcna);
-    g_last_plan[4] = p.full | (p.tk8 ? 2 : 0) | (p.wgs << 2) | (p.nw == 8 ? 32 : 0); g_last_plan[5] = (int)(1000.0 * pop); g_last_plan[6] = (int)std::min<int64_t>(occ, 2147483647); g_last_plan[7] = 1;
+    g_last_plan[0] = p.txy; g_last_plan[1] = p.tz; g_last_plan[2] = p.cap; g_last_plan[3] = (int)lds_bytes(p.cap, M, tk8, p.rw, fcna);
+    g_last_plan[4] = p.full | (p.tk8 ? 2 : 0) | (p.wgs << 2); g_last_plan[5] = (int)(1000.0 * pop); g_last_plan[6] = (int)std::min<int64_t>(occ, 2147483647); g_last_plan[7] = 1;
     return p;
 }
 
@@ -1545,8 +1428,7 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
         list_mode = 1;
     }
     const dim3 grid((unsigned)(per * 8));
-    const size_t lds1 = lds_bytes(plan.cap, count ? 1 : M, plan.tk8, plan.rw, plan.nw, pattern != nullptr); // first pass (four or eight waves per workgroup)
-    const size_t lds2 = lds_bytes(plan.cap, count ? 1 : M, plan.tk8, plan.rw, 4, pattern != nullptr);       // slice pass: always four
+    const size_t lds = lds_bytes(plan.cap, count ? 1 : M, plan.tk8, plan.rw, pattern != nullptr);
     const int cen_lo = cg.cen_hi > cg.cen_lo ? cg.cen_lo : 0, cen_hi = cg.cen_hi > cg.cen_lo ? cg.cen_hi : 0x7fffffff;
     const int Mi = (int)M, wp = fill_pads ? (g_lane_ids_only ? 3 : 1) : 0; // bit 1: the wide instance neither computes nor stores the distances (lane_ids_only)
     const float negc = -plan.mid;
@@ -1558,41 +1440,33 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
     const Shape ts2 = make_shape(ts.txy, 1, nt[1], nt2b);
     const bool indirect = !cg.pk; // CellGrid::ix
     const lane::IndirectSrc isrc{cg.ix, cg.iy, cg.iz, cg.imv, cg.order};
-#define MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, NW, IND, GRID, JT0, ...)                                                             \
+#define MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, IND, GRID, JT0, ...)                                                                 \
     do {                                                                                                                                  \
         if (lds > 60 * 1024) /* above the default dynamic-LDS limit: raise it for the instance about to run */                            \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, NW, IND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, NW, IND>), GRID, dim3((NW) * 64), lds, st, cg.pk, cg.cell_start, b, \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND>), GRID, dim3(NW * 64), lds, st, cg.pk, cg.cell_start, b, \
                            cg.g, rc, negc, plan.T, verlet, dist, nn, Mi, wp, plan.cap, cg.flags, nullptr, __VA_ARGS__, pattern, tf.cna_todo, JT0, plan.rw, tile_base, plan.listed_sink, \
                            cen_lo, cen_hi, isrc); \
     } while (0)
-#define MDH_LANE_PASS(COUNT, TRI, LOOP, FCNA, TK8, NW, GRID, JT0, ...)                                                                         \
+#define MDH_LANE_PASS(COUNT, TRI, LOOP, FCNA, TK8, GRID, JT0, ...)                                                                        \
     do {                                                                                                                                  \
-        const size_t lds = (NW) == 8 ? lds1 : lds2;                                                                                       \
-        if (indirect) MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, NW, true, GRID, JT0, __VA_ARGS__);                                     \
-        else MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, NW, false, GRID, JT0, __VA_ARGS__);                                             \
+        if (indirect) MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, true, GRID, JT0, __VA_ARGS__);                                         \
+        else MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, false, GRID, JT0, __VA_ARGS__);                                                 \
     } while (0)
     // first pass: one tile per workgroup — all tiles, or the list of live ones, whose length only the device knows: the grid
     // is cut for the expected number and a walked launch stands by for what a longer list leaves over (it leaves at once
     // otherwise); second pass: one-cell slices of what the first listed
-#define MDH_LANE_LAUNCH_NW(COUNT, TRI, FCNA, TK8, NW)                                                                                     \
+#define MDH_LANE_LAUNCH(COUNT, TRI, FCNA, TK8)                                                                                            \
     do {                                                                                                                                  \
         if (list_mode) {                                                                                                                  \
-            MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, NW, grid, 0, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
+            MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, grid, 0, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
             if ((int64_t)per * 8 < ntiles)                                                                                                \
-                MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, NW, dim3(512), per, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
+                MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, dim3(512), per, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
         } else {                                                                                                                          \
-            MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, NW, grid, 0, nt0_run, nt[1], nt[2], ts, nullptr, slot + ntiles, 0, max_count, flagged, nullptr, 0, 1, 2); \
+            MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, grid, 0, nt0_run, nt[1], nt[2], ts, nullptr, slot + ntiles, 0, max_count, flagged, nullptr, 0, 1, 2); \
         }                                                                                                                                 \
-        MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, 4, grid2, 0, nt[0], nt[1], nt2b, ts2, nullptr, cg.flags + 2, 1, max_count, flagged2, flagged, nt[2], nsub, 3); \
+        MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, grid2, 0, nt[0], nt[1], nt2b, ts2, nullptr, cg.flags + 2, 1, max_count, flagged2, flagged, nt[2], nsub, 3); \
     } while (0)
-#define MDH_LANE_LAUNCH(COUNT, TRI, FCNA, TK8) MDH_LANE_LAUNCH_NW(COUNT, TRI, FCNA, TK8, 4)
-#ifdef MDH_LANE_NW8 // measuring build (make nw8): the eight-wave instances are compiled in and MDH_LANE_NW=8 selects them
-    if (plan.nw == 8) { // (one-byte instance without the fused CNA: plan_lane)
-        if (count) { if (b.tri) MDH_LANE_LAUNCH_NW(true, true, false, true, 8); else MDH_LANE_LAUNCH_NW(true, false, false, true, 8); }
-        else { if (b.tri) MDH_LANE_LAUNCH_NW(false, true, false, true, 8); else MDH_LANE_LAUNCH_NW(false, false, false, true, 8); }
-    } else
-#endif
     if (count) {
         if (plan.tk8) { if (b.tri) MDH_LANE_LAUNCH(true, true, false, true); else MDH_LANE_LAUNCH(true, false, false, true); }
         else { if (b.tri) MDH_LANE_LAUNCH(true, true, false, false); else MDH_LANE_LAUNCH(true, false, false, false); }
@@ -1606,7 +1480,6 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
 #undef MDH_LANE_PASS
 #undef MDH_LANE_PASS_I
 #undef MDH_LANE_LAUNCH
-#undef MDH_LANE_LAUNCH_NW
     MDH_HIP(hipGetLastError());
     // what the two passes listed for the thread-per-atom code (k_neighbor_tiles), in the tiling of the second pass
     tf.flag = reinterpret_cast<const unsigned char *>(flagged2); // (non-null: "a tiled kernel ran"; the per-tile byte flags are not used with a list)

@@ -104,12 +104,8 @@ static int parse_structures(const char *s)
 
 using namespace mdh;
 
-namespace mdh { void ptm_debug_order_cap(int cap); }
-extern "C" int mdh_debug_set_ptm_order_cap(int cap)
-{
-    mdh::ptm_debug_order_cap(cap);
-    return MDH_OK;
-}
+namespace mdh { int ptm_debug_order_cap(int cap); }
+extern "C" int mdh_debug_set_ptm_order_cap(int cap) { return mdh::ptm_debug_order_cap(cap); }
 
 extern "C" int mdh_ptm_flags(const char *structure) { return parse_structures(structure); }
 

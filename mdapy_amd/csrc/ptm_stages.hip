@@ -204,9 +204,9 @@ template <class P> __device__ bool face_solid_angle_2d_regs(int i, int n, const 
 }
 
 // REDO = second pass over the atoms whose polygons outgrew the first pass's storage (flag set), with room for 28 vertices
-// ROUNDS (DIM 2; the name is historic): the polygon cached in registers, face_solid_angle_2d_regs
-template <bool TRI, int CAP, bool REDO, int DIM, bool ROUNDS = false>
-__global__ __launch_bounds__(ORD_THREADS, (CAP == 8 ? (ROUNDS ? 3 : 4) : (ROUNDS && CAP == 10 ? 3 : 1))) void k_ptm_order_faces(const double *__restrict__ x, const double *__restrict__ y,
+// DIM 2: the first pass's polygon cached in registers, face_solid_angle_2d_regs
+template <bool TRI, int CAP, bool REDO, int DIM>
+__global__ __launch_bounds__(ORD_THREADS, (CAP == 8 ? (DIM == 2 ? 3 : 4) : (DIM == 2 && CAP == 10 ? 3 : 1))) void k_ptm_order_faces(const double *__restrict__ x, const double *__restrict__ y,
                                                                  const double *__restrict__ z, int64_t N, DBox b,
                                                                  const int *__restrict__ verlet, int64_t M, int8_t *__restrict__ orders,
                                                                  int *__restrict__ nbr, unsigned char *__restrict__ redo,
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(ORD_THREADS, (CAP == 8 ? (ROUNDS ? 3 : 4) : (ROUNDS
         double a = 0;
         int peak = 0;
         bool fits;
-        if constexpr (DIM == 2 && ROUNDS && CAP <= 15) // (the second pass's 28-vertex polygons stay in the stripe: 112 registers of cache)
+        if constexpr (DIM == 2 && CAP <= 15) // (the second pass's 28-vertex polygons stay in the stripe: 112 registers of cache)
             fits = face_solid_angle_2d_regs(f, cnt, S.pts[slot], S.nsq[slot], k, poly, &a, (CAP > 8 && !REDO) ? &peak : nullptr);
         else if constexpr (DIM == 2)
             fits = ptmc::face_solid_angle_2d(f, cnt, S.pts[slot], S.nsq[slot], k, poly, &a, (CAP > 8 && !REDO) ? &peak : nullptr);
@@ -1670,9 +1670,8 @@ void ptm_compose_match_tables(const ptmc::Tables &T, void *out)
 }
 
 static int g_order_cap = 10; // polygon vertices in the first pass (10: faces of up to ten corners — all of a crystal's — stay in it); larger faces take the second pass
-static int g_order_dim = 2;  // 2: polygons in the coordinates of their own plane; 3: in space (the form of rounds 1-2, kept for A/B)
+static int g_order_dim = 2;  // 2: polygons in the coordinates of their own plane; 3: in space (the form of rounds 1-2, which the tests compare the 2-D form with)
 static bool g_order_auto = true;
-static bool g_order_rounds = true; // the polygon cached in registers (face_solid_angle_2d_regs); false: in the LDS stripe only (A/B, the areas are the same bits)
 // Automatic choice of the first pass: eight-vertex polygons run at four waves per SIMD (128 VGPRs, 22 KB of LDS) and are 5 %
 // faster on crystals, whose faces stay small; a gas or a glass sends half its atoms to the second pass with them (2.2x
 // slower).  Every call counts the atoms that had a face of more than eight vertices; the count of the previous call with the
@@ -1681,17 +1680,20 @@ static bool g_order_rounds = true; // the polygon cached in registers (face_soli
 static int *g_order_stat = nullptr; // pinned: [0] atoms with a face of > 8 vertices in the last finished call
 static int64_t g_order_stat_n = -1; // ... which had this many atoms
 // test / measurement hook (mdh_debug_set_ptm_order_cap): 0 -> automatic; |cap| -> 5, 8, 10 or 15 vertices; a NEGATIVE value selects the 3-D polygons
-void ptm_debug_order_cap(int cap)
+int ptm_debug_order_cap(int cap)
 {
-    g_order_rounds = !(cap >= 100); // 100 + cap: the plain clip loop (100 alone: plain loop, automatic cap)
-    if (cap >= 100) cap -= 100;
+    if (cap >= 100) {
+        set_error("mdh_debug_set_ptm_order_cap: cap must be below 100");
+        return MDH_ERR_ARG;
+    }
     g_order_auto = cap == 0;
     g_order_dim = cap < 0 ? 3 : 2;
     const int c = cap < 0 ? -cap : cap;
     g_order_cap = cap == 0 ? 10 : c <= 5 ? 5 : c <= 8 ? 8 : c <= 10 ? 10 : 15;
+    return MDH_OK;
 }
 
-template <bool TRI, int CAP, int DIM, bool ROUNDS>
+template <bool TRI, int CAP, int DIM>
 static int launch_ptm_order_as(const double *dx, const double *dy, const double *dz, int64_t N, const DBox &b, const int *dv, int64_t M, int8_t *dord,
                                int *dnbr, unsigned char *redo, int *redo_count, hipStream_t st)
 {
@@ -1699,11 +1701,11 @@ static int launch_ptm_order_as(const double *dx, const double *dy, const double 
     const dim3 grid((unsigned)((N + ORD_APB - 1) / ORD_APB)), block(ORD_THREADS);
     const dim3 small(grid.x < 1024u ? grid.x : 1024u);
     // the second pass may ask for more than the 64 KB of dynamic LDS a launch gets by default
-    MDH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ptm_order_faces<TRI, 28, true, DIM, ROUNDS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    MDH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ptm_order_faces<TRI, 28, true, DIM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(order_lds_bytes<28, DIM>())));
     const size_t lds1 = order_lds_bytes<CAP, DIM>(), lds2 = order_lds_bytes<28, DIM>();
-    hipLaunchKernelGGL((k_ptm_order_faces<TRI, CAP, false, DIM, ROUNDS>), grid, block, lds1, st, dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count);
-    hipLaunchKernelGGL((k_ptm_order_faces<TRI, 28, true, DIM, ROUNDS>), small, block, lds2, st, dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count);
+    hipLaunchKernelGGL((k_ptm_order_faces<TRI, CAP, false, DIM>), grid, block, lds1, st, dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count);
+    hipLaunchKernelGGL((k_ptm_order_faces<TRI, 28, true, DIM>), small, block, lds2, st, dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count);
     MDH_HIP(hipGetLastError());
     return MDH_OK;
 }
@@ -1724,11 +1726,7 @@ int launch_ptm_order(const double *dx, const double *dy, const double *dz, int64
         int *count; int cap; int64_t n; hipStream_t st;
         ~Note() { (void)hipMemcpyAsync(g_order_stat, cap > 8 ? count + 1 : count, sizeof(int), hipMemcpyDeviceToHost, st); g_order_stat_n = n; }
     } note{redo_count, ran_cap, N, st};
-#define MDH_ORD(TRI, CAP, DIM)                                                                                                                  \
-    do {                                                                                                                                       \
-        if (DIM == 2 && g_order_rounds) return launch_ptm_order_as<TRI, CAP, DIM, (DIM == 2)>(dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count, st); \
-        return launch_ptm_order_as<TRI, CAP, DIM, false>(dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count, st);                          \
-    } while (0)
+#define MDH_ORD(TRI, CAP, DIM) return launch_ptm_order_as<TRI, CAP, DIM>(dx, dy, dz, N, b, dv, M, dord, dnbr, redo, redo_count, st)
 #define MDH_ORD_CAP(TRI, DIM)                                                                                                                  \
     do {                                                                                                                                       \
         if (g_order_cap == 5) MDH_ORD(TRI, 5, DIM); /* test hook: a first pass so small that most atoms take the second one */                 \

@@ -1,9 +1,8 @@
 #!/usr/bin/env python
 """The headline step as two C-ABI calls (build_neighbor, then fcna) against ONE fused call (mdh_build_neighbor_fcna: the label of a
 centre worked out inside the tile kernel).  python tools/fused_ab.py [cells] [sigma] [steps]
-NB_LIB=<path>: another build of the library (make -C mdapy_amd/csrc fcna64: the fused label with double-precision pair tests, as
-until round 5).  Prints ms per step (wall, stream idle at both ends), the ranges of the library's own HIP events, and whether
-lists and labels of the two forms are identical."""
+NB_LIB=<path>: another build of the library.  Prints ms per step (wall, stream idle at both ends), the ranges of the library's own
+HIP events, and whether lists and labels of the two forms are identical."""
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Instruction ledger of the headline instance of the tile neighbour kernel (k_neighbor_lane<COUNT=0, TRI=0, LOOP=0, FCNA=0, TK8=1, NW=4>):
+"""Instruction ledger of the headline instance of the tile neighbour kernel (k_neighbor_lane<COUNT=0, TRI=0, LOOP=0, FCNA=0, TK8=1, IND=1>):
 the gfx950 ISA of mdapy_amd/csrc/neighbor_lane.hip with line tables, every instruction attributed to a phase of the kernel by the
 source line it came from (inlined helpers by their own lines), counted by unit.  Static counts; the kernel is straight-line per tile and
 per chunk of 64 centres, so a wave that takes one chunk of a tile executes the front phases once and the chunk phases once — the
@@ -10,7 +10,7 @@ import os, re, subprocess, sys, tempfile, collections
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "mdapy_amd", "csrc", "neighbor_lane.hip")
-KERNEL = "_ZN3mdh4lane15k_neighbor_laneILb0ELb0ELb0ELb0ELb1ELi4EE"
+KERNEL = "_ZN3mdh4lane15k_neighbor_laneILb0ELb0ELb0ELb0ELb1ELb1EE"
 
 # phases by source line of neighbor_lane.hip (first line of the range); helpers that are inlined carry their own lines
 def build_phase_table():
@@ -31,7 +31,7 @@ def build_phase_table():
         (line_of("__device__ __forceinline__ int run_slots"), "misc helpers"),
         (line_of("__device__ __forceinline__ bool sqrt_fast_ok"), "write-out: f64 distance + sqrt"),
         (line_of("template <bool SELF, bool TRI>"), "band: f64 re-decision (rare)"),
-        (line_of("template <bool TRI, int NN, class Index>"), "fused CNA (not in this instance)"),
+        (line_of("template <int NN, class Index>"), "fused CNA (not in this instance)"),
         (line_of("__device__ __forceinline__ int bit_select"), "write-out: quad transpose + stores"),
         (kern, "front: tile / halo-cell coordinates, first loads"),
         (line_of("hc(tid) = (unsigned)cnt;", kern), "front: workgroup scan, run table"),
