@@ -376,6 +376,31 @@ int mdh_rdf_streaming(const double *x, const double *y, const double *z, const i
                       const double *box9, const double *origin3, const int *boundary3, double *g, int ntype,
                       double rc, int nbin, int space, void *stream);
 
+/* ---- _bond_analysis ----------------------------------------------------- */
+/* replaces _bond_analysis.compute_bond                     src/bond_analysis.cpp:8-137
+ * box9 / origin3 / boundary3 are host arrays.  ADDS the bond-length (j > i, r <= rc) and bond-angle (both r <= rc) counts into
+ * length_hist / angle_hist (nbin u64 each).  The angle bin is the reference's floor(acos(c) * 180 / PI / delta_theta) clamped
+ * to nbin - 1, exactly (mdh_debug_angle_edges); a triplet whose cosine is NaN (a zero distance) is not counted. */
+int mdh_bond_analysis(const double *x, const double *y, const double *z, int64_t N, const double *box9, const double *origin3,
+                      const int *boundary3, const int *verlet, const double *dist, const int *nn, int64_t M, double delta_r,
+                      double delta_theta, double rc, int nbin, unsigned long long *length_hist, unsigned long long *angle_hist,
+                      int space, void *stream);
+/* replaces _bond_analysis.compute_adf                      src/bond_analysis.cpp:139-279
+ * type (N) 0-based codes; patterns_host (npattern x 3: centre A, j-type B, k-type C) and ranges_host (npattern x 4:
+ * rij_min, rij_max, rik_min, rik_max, inclusive) are host arrays.  ADDS into hist (npattern x nbin u64).  B == C: slot pairs
+ * jj < kk only (row order matters); B != C: every kk != jj.  Any number of patterns (32 per kernel launch). */
+int mdh_angular_distribution(const double *x, const double *y, const double *z, int64_t N, const double *box9,
+                             const double *origin3, const int *boundary3, const int *verlet, const double *dist, const int *nn,
+                             const int *type, int64_t M, double delta_theta, const int *patterns_host, const double *ranges_host,
+                             int npattern, int nbin, unsigned long long *hist, int space, void *stream);
+/* test hook (host code only, no device needed): out[k], k = 0 .. nbin-2, ascending, = t_m with m = nbin-1-k: the smallest
+ * double c in [-1, 1] whose angle bin min(floor(((acos(c) * 180.0) / PI) * (1.0 / delta_theta)), nbin - 1) is below m, with
+ * the C library's acos.  The kernels bin a cosine c as #{m : c < t_m}. */
+int mdh_debug_angle_edges(int nbin, double delta_theta, double *out);
+/* test hook: bond analysis / ADF, 0 = rows of up to 512 slots staged in LDS (default), 1 = every row through the wide-row
+ * path (its slots read from HBM per pair); any other value returns MDH_ERR_ARG */
+int mdh_debug_set_bond_variant(int variant);
+
 /* ---- _wcp ------------------------------------------------------------- */
 /* replaces _wcp.get_wcp                                    src/warren_cowley_parameter.cpp:9-80; wcp (ntype,ntype) */
 int mdh_wcp(const int *verlet, const int *nn, const int *type, int64_t N, int64_t M, int ntype, double *wcp,

@@ -87,6 +87,10 @@ _SIGNATURES = {
     "mdh_rdf": [vp, vp, vp, vp, i64, i64, vp, cint, dbl, cint, cint, vp],
     "mdh_rdf_single_species": [vp, vp, vp, i64, i64, vp, dbl, cint, cint, vp],
     "mdh_rdf_streaming": [vp, vp, vp, vp, i64, vp, vp, vp, vp, cint, dbl, cint, cint, vp],
+    "mdh_bond_analysis": [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, dbl, dbl, dbl, cint, vp, vp, cint, vp],
+    "mdh_angular_distribution": [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, dbl, vp, vp, cint, cint, vp, cint, vp],
+    "mdh_debug_angle_edges": [cint, dbl, vp],
+    "mdh_debug_set_bond_variant": [cint],
     "mdh_wcp": [vp, vp, vp, i64, i64, cint, vp, cint, vp],
     "mdh_wcp_counts": [vp, vp, vp, vp, i64, i64, cint, vp, cint, vp],
     "mdh_knn": [vp, vp, vp, i64, vp, vp, vp, cint, vp, vp, cint, vp],

@@ -18,7 +18,9 @@ import numpy as np
 from . import policy
 from . import tool_function as tool
 from .ackland_jones_analysis import AcklandJonesAnalysis
+from .angular_distribution_function import AngularDistributionFunction
 from .atomic_temperature import AtomicTemperature
+from .bond_analysis import BondAnalysis
 from .box import Box
 from .centro_symmetry_parameter import CentroSymmetryParameter
 from .cluster_analysis import ClusterAnalysis
@@ -91,8 +93,20 @@ _ARGS = {
                                         "a_face_area_threshold", "r_face_area_threshold", "identify_liquid"),
     "cal_radial_distribution_function": ("rc", "nbin", "max_neigh", "streaming"),
     "cal_warren_cowley_parameter": ("rc", "max_neigh"),
+    "cal_bond_analysis": ("rc", "nbin", "max_neigh"),
+    "cal_angular_distribution_function": ("rc_dict", "nbin", "max_neigh"),
     "average_by_neighbor": ("average_rc", "property_name"),
 }
+
+
+def _adf_reach(rc_dict):
+    """the list cutoff of an angular distribution function: the largest number of all its ranges (system.py:2214); None if
+    there is none to read"""
+    try:
+        values = np.asarray(list(rc_dict.values()), dtype=float)
+        return float(values.max()) if values.size else None
+    except (AttributeError, TypeError, ValueError):
+        return None
 
 
 def _position_columns(xyz):
@@ -294,6 +308,11 @@ class System:
             twin._forget(_LIST)
         bound = dict(zip(_ARGS.get(name, ()), args), **kwargs)
         reach = bound.get("rc", bound.get("average_rc"))
+        if name == "cal_angular_distribution_function":
+            reach = _adf_reach(bound.get("rc_dict"))
+        if name in ("cal_bond_analysis", "cal_angular_distribution_function") and isinstance(reach, (int, float, np.integer, np.floating)) \
+                and "rc" in self.__dict__ and self.rc >= reach and "_list_cutoff" not in self.__dict__:
+            return None  # (a k-nearest list beside a stale rc is reused as it is: its rows are not symmetric, so j > i depends on numbering)
         if isinstance(reach, (int, float, np.integer, np.floating)) and reach > 0 and \
                 not policy.is_single(policy.axis_copies(self.box, 2.0 * float(reach))):
             return None  # the build would search a replica: the ordering key cannot follow
@@ -823,6 +842,37 @@ class System:
         """-> WarrenCowleyParameter (``WCP`` matrix)"""
         self._require_cutoff_list(rc, max_neigh)
         job = WarrenCowleyParameter(self.verlet_list, self.neighbor_number, self._get_compute_view()[1])
+        job.compute()
+        return job
+
+    @_on_twin
+    def cal_bond_analysis(self, rc, nbin, max_neigh=None):
+        """-> BondAnalysis (``bond_length_distribution``, ``bond_angle_distribution``, ``r_length``, ``r_angle``; int64 counts)"""
+        if not float(rc) > 0:
+            raise ValueError(f"rc must be positive, got {rc}.")
+        if int(nbin) < 1:
+            raise ValueError(f"nbin must be at least 1, got {nbin}.")
+        self._require_cutoff_list(rc, max_neigh)
+        cell, frame = self._get_compute_view()
+        job = BondAnalysis(frame, cell, rc, nbin, self.verlet_list, self.distance_list, self.neighbor_number)
+        job.compute()
+        return job
+
+    @_on_twin
+    def cal_angular_distribution_function(self, rc_dict, nbin, max_neigh=None):
+        """-> AngularDistributionFunction (``bond_angle_distribution`` npattern x nbin, int64, ``r_angle``).  ``rc_dict`` maps
+        ``"A-B-C"`` (A the centre) to ``[rij_min, rij_max, rik_min, rik_max]``"""
+        assert "element" in self.data.columns, "Data must contain element column."
+        rc = _adf_reach(rc_dict)
+        if rc is None:
+            raise ValueError("rc_dict must map 'A-B-C' patterns to [rij_min, rij_max, rik_min, rik_max].")
+        if not rc > 0:
+            raise ValueError(f"the largest cutoff of rc_dict must be positive, got {rc}.")
+        if int(nbin) < 1:
+            raise ValueError(f"nbin must be at least 1, got {nbin}.")
+        self._require_cutoff_list(rc, max_neigh)
+        cell, frame = self._get_compute_view()
+        job = AngularDistributionFunction(frame, cell, rc_dict, nbin, self.verlet_list, self.distance_list, self.neighbor_number)
         job.compute()
         return job
 
