@@ -248,6 +248,12 @@ int mdh_slab_append_ghosts_static(const double *msg_from_left, const double *msg
                                   double *const *columns_host_array_of_device_pointers, int ncol, int64_t *gid, int64_t n_owned,
                                   void *stream);
 int mdh_slab_overflow_check(void);
+/* The result arrays a decomposed step keeps from call to call (device pointers: verlet and dist n x max_neigh, nn n; x n, the local
+ * positions): every slot in [first, n) that holds an ABSENT atom (x = NaN) and still has a count from an earlier step — the slot held
+ * a ghost with a row then — gets count 0 and pads (-1 / pad).  Slots whose count reads 0 are left alone: they must hold pads already
+ * (arrays that started as pads and were written by the neighbor builds do).  One launch on `stream`.  No reference counterpart. */
+int mdh_slab_reset_absent_rows(const double *x, int *verlet, double *dist, int *nn, int64_t first, int64_t n, int64_t max_neigh, double pad,
+                               void *stream);
 
 /* ---- atom order (csrc/order.hip).  The reference's linked-list cell build (src/neighbor.cpp:64-100) and its consumers are
  * indifferent to the order in which atoms arrive; these kernels' gathers are not.  No reference counterpart: the host layer
@@ -427,7 +433,12 @@ int mdh_knn_keyed(const double *x, const double *y, const double *z, int64_t N, 
  * >= mdh_knn_rows_width(k) for a search that is to FILL them.  *radius (host): in — > 0: the buffers hold every atom's neighbours
  * inside that radius for THESE positions in THIS box (the caller vouches for it), the build is skipped; 0: not yet — out: the radius
  * of what the buffers hold now, 0 when they hold nothing usable (a small system, a box too thin, k > 18: the cell walk took the
- * call).  Results are those of mdh_knn_keyed in every case; a query the rows cannot finish takes the cell walk. */
+ * call).  Results are those of mdh_knn_keyed in every case; a query the rows cannot finish takes the cell walk.  counts_io need
+ * not be initialised: a build zeroes it first, so an atom the build does not bin (x = NaN) or gives no neighbour (another
+ * coordinate NaN) has count 0 and takes the cell walk too.  An atom with a NaN coordinate appears in no row, and its own row is
+ * what the cell walk writes for a query without neighbours: ids -1, distances -1.0 (fast_knn.cpp:885-888), on either path.
+ * An M_io that is not a positive multiple of four returns MDH_ERR_ARG (the rows are read in 16-byte groups).  The path's
+ * back-off table and its one read-back word are per host thread. */
 int mdh_knn_keyed_rows(const double *x, const double *y, const double *z, int64_t N, const double *box9, const double *origin3,
                        const int *boundary3, int k, int *indices, double *distances, const int64_t *key, int *rows_io, int *counts_io,
                        int M_io, double *radius, int space, void *stream);

@@ -67,6 +67,7 @@ _SIGNATURES = {
     "mdh_translate_rows": [vp, vp, vp, vp, i64, i64, vp, vp, vp, cint, vp],
     "mdh_slab_append_ghosts_static": [vp, vp, i64, vp, cint, vp, i64, vp],
     "mdh_slab_overflow_check": [],
+    "mdh_slab_reset_absent_rows": [vp, vp, vp, vp, i64, i64, i64, dbl, vp],
     "mdh_build_neighbor_keyed": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, vp, vp, i64, cint, vp, cint, vp],
     "mdh_build_neighbor_fcna": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, vp, vp, i64, cint, vp, vp, cint, vp],
     "mdh_neighbor_count": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, vp, cint, vp],

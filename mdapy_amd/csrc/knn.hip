@@ -542,7 +542,7 @@ __global__ void k_knn(const double *__restrict__ xs, const double *__restrict__ 
             for (int u = 0; u < 8; ++u) {
                 const double dx = cx[u] - w0, dy = cy[u] - w1, dz = cz[u] - w2;
                 d2s[u] = dx * dx + dy * dy + dz * dz;
-                const bool live = q0 + u < se && !(cj[u] == self && d2s[u] == 0.0) && !(d2s[u] > bound);
+                const bool live = q0 + u < se && !(cj[u] == self && d2s[u] == 0.0) && d2s[u] <= bound; // (a NaN — an atom or a query without a position — is never listed)
                 todo |= live ? 1u << u : 0u;
             }
             while (todo) {
@@ -726,6 +726,10 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
     const double radius_in = radius ? *radius : 0.0;
     if (radius) *radius = 0.0;
     if (N < 0 || N >= 2147483647LL || k <= 0 || k > 64) { set_error("mdh_knn: need 1 <= k <= 64"); return MDH_ERR_ARG; }
+    if (rows_io && counts_io && (M_io <= 0 || M_io % 4 != 0)) { // (k_knn_rows reads a row in 16-byte groups)
+        set_error("mdh_knn_keyed_rows: the row width must be a positive multiple of four");
+        return MDH_ERR_ARG;
+    }
     DBox b;
     MDH_TRY(make_box(b, box9, origin3, boundary3));
     if (N == 0)
@@ -758,13 +762,13 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
         // were built for nothing: the share of the last search with this (N, k) decides — more than 0.5 %, and the next 15 searches
         // of the signature walk the cells at once (then one more try)
         struct Sig { int64_t N; int k, pbc; double vol; int left_pct, skip; };
-        static Sig sigs[16] = {};
+        static thread_local Sig sigs[16] = {}; // (per host thread, as g_window_violations and the tile plan are: no call sees another's half-written entry)
         Sig *sig = nullptr;
         const int pbc_bits = (b.pbc[0] ? 1 : 0) | (b.pbc[1] ? 2 : 0) | (b.pbc[2] ? 4 : 0);
         for (auto &e : sigs)
             if (e.N == N && e.k == k && e.pbc == pbc_bits && e.vol == vol) sig = &e;
         if (!sig) {
-            static int next = 0;
+            static thread_local int next = 0;
             sig = &sigs[next++ % 16];
             *sig = Sig{N, k, pbc_bits, vol, 0, 0};
         }
@@ -776,13 +780,16 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
             double *rdist = reuse ? nullptr : sc.alloc_n<double>((size_t)N * M);
             Pos4 *w4 = sc.alloc_n<Pos4>((size_t)N);
             only = sc.alloc_n<unsigned char>((size_t)N);
-            static int *pinned = nullptr; // the number of queries left for the cell walk: the one word this path reads back
+            static thread_local int *pinned = nullptr; // the number of queries left for the cell walk: the one word this path reads back (per host thread: two searches never share it)
             if (!pinned && hipHostMalloc(reinterpret_cast<void **>(&pinned), sizeof(int), hipHostMallocDefault) != hipSuccess) pinned = nullptr;
             if (sc.failed() || !pinned)
                 return sc.failed() ? sc.error() : MDH_ERR_HIP;
             MDH_HIP(hipMemsetAsync(nflag, 0, sizeof(int), st));
             if (!reuse) {
                 ProfRange pr("knn_rows_build", st);
+                // an atom the build does not bin (a NaN coordinate) gets no row and no count: 0, so that k_knn_rows flags it for the
+                // cell walk instead of reading a row nobody wrote
+                MDH_HIP(hipMemsetAsync(rnn, 0, (size_t)N * sizeof(int), st));
                 MDH_TRY(neighbor_rows_device(sc, dx, dy, dz, N, b, r, rows, rdist, rnn, M, nullptr, true));
             }
             if (kept && radius) *radius = r;

@@ -1746,6 +1746,9 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
         return sc.error();
     hipStream_t st = sc.stream();
     MDH_HIP(hipMemsetAsync(dmax, 0, sizeof(int), st));
+    // an absent atom (x = NaN) takes no cell and no kernel writes its count: 0, not what the caller's buffer held — the width below is
+    // the largest count of ALL N entries, and the labels behind the build read every atom's
+    MDH_HIP(hipMemsetAsync(dn, 0, (size_t)N * sizeof(int), st));
     CellGrid cg;
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
     {

@@ -212,6 +212,37 @@ extern "C" int mdh_slab_append_ghosts_static(const double *msg_left, const doubl
     return MDH_OK;
 }
 
+// The slots of ABSENT atoms (x = NaN) among rows [first, n) of a step's kept result arrays back to what the step promises for them:
+// count 0, pads.  The slot may have held a ghost with a row in the step before.  Only rows with a count are written (the arrays start
+// out as pads and a kernel that writes a row gives it its count), so a step costs one pass over x and nn of the ghost block.
+namespace mdh {
+__global__ __launch_bounds__(256) void k_slab_reset_absent(const double *__restrict__ x, int *__restrict__ verlet, double *__restrict__ dist,
+                                                           int *__restrict__ nn, int64_t first, int64_t n, int64_t M, double pad)
+{
+    const int64_t i = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || x[i] == x[i] || nn[i] == 0)
+        return;
+    int *__restrict__ v = verlet + i * M;
+    double *__restrict__ d = dist + i * M;
+    for (int64_t s = 0; s < M; ++s) { v[s] = -1; d[s] = pad; }
+    nn[i] = 0;
+}
+} // namespace mdh
+
+extern "C" int mdh_slab_reset_absent_rows(const double *x, int *verlet, double *dist, int *nn, int64_t first, int64_t n, int64_t max_neigh, double pad,
+                                          void *stream)
+{
+    if (!x || !verlet || !dist || !nn || first < 0 || n < first || n >= 2147483647LL || max_neigh <= 0) {
+        set_error("mdh_slab_reset_absent_rows: bad arguments");
+        return MDH_ERR_ARG;
+    }
+    if (n > first)
+        hipLaunchKernelGGL(k_slab_reset_absent, dim3(grid_for(n - first, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, verlet, dist, nn, first,
+                           n, max_neigh, pad);
+    MDH_HIP(hipGetLastError());
+    return MDH_OK;
+}
+
 // MDH_ERR_ARG (and the flag cleared) if a halo message appended by this thread's mdh_slab_append_ghosts_static calls announced more
 // atoms than its capacity since the last check; sees the appends that have COMPLETED on the device (no synchronisation here)
 extern "C" int mdh_slab_overflow_check(void)

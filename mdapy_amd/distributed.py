@@ -537,9 +537,12 @@ def neighbor_cna_step(dec: SlabDecomposition, x, y, z, gid, rc: float, max_neigh
     ``torch.cuda.synchronize(); dec.check_halo()`` (the last step has no successor to report it).
 
     reuse_buffers: the four result arrays are the SAME tensors from call to call (kept on `dec`, as a caller who allocates his
-    outputs once would have them — bench.py's single-GPU step does): a step then starts with one fill (the labels) instead of four —
-    the ghosts' pads and zero counts of the previous step are still there, no kernel writes those rows.  The previous step's results
-    are overwritten.
+    outputs once would have them — bench.py's single-GPU step does) while (rows, max_neigh, n_owned, rc, device) stay the same: a
+    step then zeroes the labels and resets the slots of ABSENT atoms (count 0, pads: mdh_slab_reset_absent_rows, one launch over
+    the ghost block) instead of filling all four arrays.  A slot is reset because the previous step may have left a row there — a
+    ghost in a plane it shares with owned atoms gets one, the kernels behind the tile kernel write every ghost's — and the slot may
+    hold an absent atom now.  A GHOST's row stays unspecified as before: it may be the previous step's.  The previous step's
+    results are overwritten.
 
     On more than one rank with HBM-resident tensors the exchange is *static*: the ghost count never leaves the device, so
     the local arrays have ``n_owned + 2 * cap`` rows (``dom.absent_slots`` is True) of which the slots behind the ghosts
@@ -570,7 +573,14 @@ def neighbor_cna_step(dec: SlabDecomposition, x, y, z, gid, rc: float, max_neigh
     sig = (n, int(max_neigh), dom.n_owned, float(rc), str(dom.x.device), skip_ghosts)
     if kept is not None and kept[0] == sig and skip_ghosts:
         verlet, dist, nn, pattern = kept[1]
-        pattern.zero_()  # (the kernels only ever raise a label; the ghosts' pads and zero counts are the previous step's, untouched)
+        pattern.zero_()  # (the kernels only ever raise a label)
+        # a slot that held a ghost with a row may hold an ABSENT atom now: count 0 and pads for those, as a fresh allocation has them
+        # (one launch that reads x and nn of the ghost block; a ghost's own row stays unspecified, stale or not)
+        if getattr(dom, "absent_slots", False):
+            from . import _lib
+
+            _lib.check(_lib.lib().mdh_slab_reset_absent_rows(dom.x.data_ptr(), verlet.data_ptr(), dist.data_ptr(), nn.data_ptr(), dom.n_owned, n,
+                                                             int(max_neigh), rc + 1.0, int(t.cuda.current_stream().cuda_stream)))
     else:
         verlet = t.empty((n, max_neigh), dtype=t.int32, device=dom.x.device)
         dist = t.empty((n, max_neigh), dtype=t.float64, device=dom.x.device)

@@ -203,16 +203,22 @@ def _sorted_as_last_time(cols, where, n):
     on_dev = any(c._host_arr is None or c._dev is not None for c in cols)
     if on_dev == bool(_last_order.get("host")):
         return None  # (the permutation lives in the other memory space)
-    try:
-        arrs = [c.device_array() if on_dev else c.to_numpy() for c in cols]
-        if hasattr(kernels.order, "gather_positions"):
-            moved = list(kernels.order.gather_positions(*arrs, perm))
-        else:
-            moved = [kernels.order.permute(a, perm) for a in arrs]
-        if kernels.order.order_statistic(*moved, *where[3:]) > SORT_FAR_FRACTION:
-            return None  # another numbering after all: sort
-    except Exception:
+    arrs = [c.device_array() if on_dev else c.to_numpy() for c in cols]
+    if hasattr(kernels.order, "gather_positions"):
+        moved = list(kernels.order.gather_positions(*arrs, perm))
+    else:
+        moved = [kernels.order.permute(a, perm) for a in arrs]
+    # an absent atom (a coordinate that is NaN; infinite ones with it) is binned by neither the statistic nor a sort: the sort reports
+    # fewer atoms than N and the caller makes no twin — so must this path, which never counts (a sum of finite numbers that overflows
+    # only sends the frame to the sort)
+    if on_dev:
+        total = sum(m.dev().sum() for m in moved)
+        if not bool(total.isfinite()):
+            return None
+    elif not np.isfinite(sum(float(np.sum(m)) for m in moved)):
         return None
+    if kernels.order.order_statistic(*moved, *where[3:]) > SORT_FAR_FRACTION:
+        return None  # another numbering after all: sort
     return moved[0], moved[1], moved[2], perm, int(n)
 
 

@@ -63,11 +63,38 @@ def _build_neighbor_fcna(x, y, z, box, origin, boundary, rc, v, d, nn, pattern, 
 
 
 def _spatial_sort(x, y, z, box, origin, boundary):
-    """a stand-in for mdh_spatial_sort: ANY permutation serves the host logic that is tested with it — here cells of 3 A"""
+    """a stand-in for mdh_spatial_sort: ANY permutation serves the host logic that is tested with it — here cells of 3 A.  As the
+    kernel, it bins no ABSENT atom (x = NaN) and reports how many it binned: fewer than N, and perm is no permutation then (the
+    slots behind the binned atoms hold -1)"""
     pos = np.column_stack([_np(x), _np(y), _np(z)])
-    cells = np.floor((pos - pos.min(axis=0)) / 3.0).astype(np.int64)
-    perm = np.lexsort((-np.arange(len(pos)), cells[:, 2], cells[:, 1], cells[:, 0])).astype(np.int32)
-    return pos[perm, 0].copy(), pos[perm, 1].copy(), pos[perm, 2].copy(), perm, len(pos)
+    there = ~np.isnan(pos[:, 0])
+    cells = np.nan_to_num(np.floor((pos - np.nanmin(pos, axis=0)) / 3.0)).astype(np.int64)
+    perm = np.lexsort((-np.arange(len(pos)), cells[:, 2], cells[:, 1], cells[:, 0], ~there)).astype(np.int32)
+    n = int(there.sum())
+    perm[n:] = -1
+    return pos[perm, 0].copy(), pos[perm, 1].copy(), pos[perm, 2].copy(), perm, n
+
+
+def _order_statistic(x, y, z, box, origin, boundary):
+    """mdh_order_statistic's definition (include/mdapy_amd.h, csrc/order.hip) restated: the share of consecutive atoms (i, i + 1)
+    that lie in bins of a grid of ~64-atom bins which neither coincide nor touch (periodic axes wrap; a NaN lands in bin 0).
+    Every pair is looked at (the kernel samples every stride-th one beyond 2^18 atoms)."""
+    pos = np.column_stack([_np(x), _np(y), _np(z)])
+    n = len(pos)
+    if n < 2:
+        return 0.0
+    h, pbc = np.asarray(box, np.float64).reshape(3, 3), np.asarray(boundary).ravel() != 0
+    inv = np.linalg.inv(h)
+    thick = 1.0 / np.linalg.norm(inv, axis=0)
+    edge = np.cbrt(64.0 * abs(np.linalg.det(h)) / n)
+    nb = np.clip(np.floor(thick / edge), 1, 1024).astype(np.int64)
+    f = (pos - np.asarray(origin, np.float64)) @ inv
+    f = np.where(pbc[None, :], f - np.floor(f), f)
+    f = np.nan_to_num(np.clip(f, 0.0, 0.999999999), nan=0.0)
+    c = (f * nb[None, :]).astype(np.int64)
+    dd = np.abs(c[1:] - c[:-1])
+    dd = np.where(pbc[None, :], np.minimum(dd, nb[None, :] - dd), dd)
+    return float((dd > 1).any(axis=1).sum()) / float(n - 1)
 
 
 def _permute(values, perm, scatter=False):
@@ -91,7 +118,7 @@ def _translate_rows(rows, dist, counts, perm):
     return v, d, n
 
 
-order = _mod(order_statistic=lambda x, y, z, box, origin, boundary: 1.0, spatial_sort=_spatial_sort, permute=_permute,
+order = _mod(order_statistic=_order_statistic, spatial_sort=_spatial_sort, permute=_permute,
              translate_rows=_translate_rows)
 neighbor = _mod(
     build_neighbor=_build_neighbor,

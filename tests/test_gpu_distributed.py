@@ -182,7 +182,9 @@ def _run_rank(rank, world, torch, dist_ready=True):
     return bad, int(own.sum()), int((~own).sum())
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, target=None):
+    """one rank of a gloo group on cuda:0; target(rank, world, torch) -> (bad, a, b) (default: _run_rank; a module-level function, it
+    is pickled by name for the spawned process)"""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -193,13 +195,29 @@ def _worker(rank, world, port, q):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        q.put((rank,) + _run_rank(rank, world, torch))
+        q.put((rank,) + tuple((target or _run_rank)(rank, world, torch)))
     except Exception as e:  # pragma: no cover
         import traceback
 
         q.put((rank, [repr(e) + traceback.format_exc()[-1500:]], 0, 0))
     finally:
         dist.destroy_process_group()
+
+
+def _spawn(world, target=None):
+    """`world` processes that share the GPU and talk over gloo -> what each rank's target returned, (rank, bad, a, b)"""
+    import torch.multiprocessing as tmp
+
+    ctx = tmp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, target)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=600) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=120)
+    return res
 
 
 def test_decomposed_steps_world1_equal_the_undivided_system():
@@ -211,17 +229,7 @@ def test_decomposed_steps_world1_equal_the_undivided_system():
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_decomposed_steps_on_hip_kernels_equal_the_undivided_system(world):
-    import torch.multiprocessing as tmp
-
-    ctx = tmp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=600) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=120)
+    res = _spawn(world)
     for rank, bad, n_own, n_ghost in sorted(res):
         assert bad == [], f"rank {rank}: {bad}"
         assert n_own > 0 and n_ghost > 0
