@@ -407,6 +407,30 @@ int mdh_debug_angle_edges(int nbin, double delta_theta, double *out);
  * path (its slots read from HBM per pair); any other value returns MDH_ERR_ARG */
 int mdh_debug_set_bond_variant(int variant);
 
+/* ---- _strain ------------------------------------------------------------ */
+/* Atomic strain of a current frame against a reference frame over the REFERENCE frame's cutoff list (verlet N x M, nn N): for
+ * every atom, V and W summed over its row in list order with each frame's own minimum image (ref_box9 / ref_origin3 and
+ * cur_box9 / cur_origin3, one boundary3 for both; host arrays), F = (W V^-1)^T, s = (F^T F - I) / 2; shear (N) f64 = the von
+ * Mises invariant of s, volumetric (N) f64 = trace(s) / 3.  A row ends at nn[i] entries or at the first entry outside [0, N).
+ * An atom without neighbours gets shear 0, volumetric -0.5 (V^-1 is the identity when |det V| < 1e-12, W is zero).
+ *
+ * Positions travel as RECORDS: 4 f64 per atom (x, y, z, unused), 32-byte so that a neighbour is two 16-byte requests.  A record
+ * buffer belongs to the caller, who packs a reference frame once and hands the same records to every later call:
+ * mdh_strain_pack: records (N x 4) f64 from three columns; map9_host (9 f64, row-major, host; NULL: none) maps each position
+ * on the way, x' = (x m[0] + y m[3]) + z m[6], y' = (x m[1] + y m[4]) + z m[7], z' = (x m[2] + y m[5]) + z m[8]. */
+int mdh_strain_pack(const double *x, const double *y, const double *z, int64_t N, const double *map9_host, double *records,
+                    int space, void *stream);
+/* the strain from two record buffers (mdh_strain_pack) */
+int mdh_atomic_strain_records(const int *verlet, const int *nn, int64_t N, int64_t M, const double *ref_box9, const double *ref_origin3,
+                              const double *cur_box9, const double *cur_origin3, const int *boundary3, const double *ref_records,
+                              const double *cur_records, double *shear, double *volumetric, int space, void *stream);
+/* replaces _strain.cal_atomic_strain                        src/atomic_strain.cpp:110-217
+ * the same from six columns, packed into scratch for this call; map9_host as in mdh_strain_pack, applied to the current frame. */
+int mdh_atomic_strain(const int *verlet, const int *nn, int64_t N, int64_t M, const double *ref_box9, const double *ref_origin3,
+                      const double *cur_box9, const double *cur_origin3, const int *boundary3, const double *ref_x, const double *ref_y,
+                      const double *ref_z, const double *cur_x, const double *cur_y, const double *cur_z, const double *map9_host,
+                      double *shear, double *volumetric, int space, void *stream);
+
 /* ---- _wcp ------------------------------------------------------------- */
 /* replaces _wcp.get_wcp                                    src/warren_cowley_parameter.cpp:9-80; wcp (ntype,ntype) */
 int mdh_wcp(const int *verlet, const int *nn, const int *type, int64_t N, int64_t M, int ntype, double *wcp,

@@ -15,6 +15,7 @@ from .steinhardt_bond_orientation import SteinhardtBondOrientation
 from .polyhedral_template_matching import PolyhedralTemplateMatching
 from .radial_distribution_function import RadialDistributionFunction
 from .warren_cowley_parameter import WarrenCowleyParameter
+from .atomic_strain import AtomicStrain
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -22,5 +23,6 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
+    "AtomicStrain",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

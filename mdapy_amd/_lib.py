@@ -92,6 +92,9 @@ _SIGNATURES = {
     "mdh_angular_distribution": [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, dbl, vp, vp, cint, cint, vp, cint, vp],
     "mdh_debug_angle_edges": [cint, dbl, vp],
     "mdh_debug_set_bond_variant": [cint],
+    "mdh_strain_pack": [vp, vp, vp, i64, vp, vp, cint, vp],
+    "mdh_atomic_strain_records": [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_atomic_strain": [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
     "mdh_wcp": [vp, vp, vp, i64, i64, cint, vp, cint, vp],
     "mdh_wcp_counts": [vp, vp, vp, vp, i64, i64, cint, vp, cint, vp],
     "mdh_knn": [vp, vp, vp, i64, vp, vp, vp, cint, vp, vp, cint, vp],

@@ -383,6 +383,7 @@ void warm_csp(hipStream_t st);
 void warm_sbo(hipStream_t st);
 void warm_rdf(hipStream_t st);
 void warm_bond(hipStream_t st);
+void warm_strain(hipStream_t st);
 void warm_wcp(hipStream_t st);
 void warm_knn(hipStream_t st);
 void warm_repeat(hipStream_t st);
@@ -502,6 +503,7 @@ int mdh_warm(void)
     mdh::warm_sbo(nullptr);
     mdh::warm_rdf(nullptr);
     mdh::warm_bond(nullptr);
+    mdh::warm_strain(nullptr);
     mdh::warm_wcp(nullptr);
     mdh::warm_knn(nullptr);
     mdh::warm_repeat(nullptr);

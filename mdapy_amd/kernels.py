@@ -23,6 +23,8 @@ from . import _rdf as rdf
 from . import _repeat_cell as repeat_cell
 from . import _sbo as sbo
 from . import _sfc as sfc
+# (not in NAMES either: the oracle has no atomic strain; its tests install a restatement as kernels.strain)
+from . import _strain as strain
 from . import _structure_entropy as structure_entropy
 from . import _voronoi as voronoi
 from . import _wcp as wcp
