@@ -153,6 +153,12 @@ int mdh_parse_table(const char *text, int64_t nbytes, int text_space, int64_t nr
  * (high, low word); the field converter itself: 0 converted, 1 undecided (host must redo), 2 not a number */
 int mdh_debug_text_pow5(int q, uint64_t *out2);
 int mdh_debug_parse_double(const char *s, int64_t len, double *out);
+/* test hook (runs on the host, no GPU needed): the rule by which the cell-assignment kernel groups the atoms of a 64-atom
+ * slice under one atomic (csrc/assign_groups.hpp), applied to cells[0 .. n) slice by slice (a last short slice is padded
+ * with negative cells).  head[i] = index, inside its slice, of the lane whose atomic serves atom i; count[i] = what that
+ * atomic adds (0 for a member of a group); rank[i] = atom i's offset from the value the atomic returns.
+ * Returns the number of atomics: heads with cell >= 0. */
+int64_t mdh_debug_assign_groups(const int *cells, int64_t n, int *head, int *count, int *rank);
 
 /* ---- _neighbor -------------------------------------------------------- */
 /*

@@ -53,6 +53,7 @@ _SIGNATURES = {
     "mdh_parse_table": [vp, i64, cint, i64, cint, vp, vp, vp, i64, vp, cint, vp],
     "mdh_debug_text_pow5": [cint, vp],
     "mdh_debug_parse_double": [C.c_char_p, i64, vp],
+    "mdh_debug_assign_groups": [vp, i64, vp, vp, vp],
     "mdh_build_neighbor": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, vp, vp, i64, cint, cint, vp],
     "mdh_slab_halo_select": [vp, vp, vp, i64, vp, vp, dbl, dbl, vp, vp, vp, vp, vp, vp, i64, cint, vp],
     "mdh_hint_cell_window": [cint, dbl, dbl],
@@ -123,7 +124,7 @@ _SIGNATURES = {
     "mdh_sfc_direct_partial": [vp, vp, vp, vp, cint, i64, vp, vp, cint, dbl, dbl, cint, vp],
     "mdh_filter_by_type": [vp, vp, vp, vp, i64, i64, vp, vp, vp, cint, cint, vp],
 }
-_RESTYPES = {"mdh_last_error": C.c_char_p, "mdh_workspace_bytes": C.c_int64}
+_RESTYPES = {"mdh_last_error": C.c_char_p, "mdh_workspace_bytes": C.c_int64, "mdh_debug_assign_groups": C.c_int64}
 
 EXPORTS = tuple(_SIGNATURES)
 

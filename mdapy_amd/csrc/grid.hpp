@@ -99,6 +99,7 @@ struct TileFilter {
     int *cna_todo = nullptr;    // != nullptr (fused neighbor + fixed CNA): the mop-up kernels list the atoms they take here, count first
     int tile = 1, tile_z = 1;
     int nt[3] = {1, 1, 1};
+    int *listed_sink = nullptr; // != nullptr: the list is the tile kernel's FIRST pass's (no slice pass ran); the mop-up writes its length here (GridStats::listed_sink)
 };
 // occupied_cells: cells that hold atoms (occupied_cells_hint); 0 = assume all of them
 TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells);
@@ -111,7 +112,7 @@ struct GridStats {
     static constexpr int NBIN = 99; // v[0] = cells of the occupied region; v[1 + len] = 3-cell z-runs of that length (98: longer than 96)
     int v[NBIN];
     int last_listed = -1;   // tiles the first pass of the previous build with this (N, grid) listed for the second (-1: not known)
-    int *listed_sink = nullptr; // pinned host word the second pass of THIS build writes its count to (device-visible)
+    int *listed_sink = nullptr; // pinned host word THIS build writes that count to (device-visible): its second pass, or, when none is launched, its mop-up (TileFilter::listed_sink)
 };
 struct LanePlan {
     int txy, tz;      // tile shape in cells; txy == 0: not applicable

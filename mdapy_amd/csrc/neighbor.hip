@@ -9,7 +9,8 @@
 //   caller:  x,y,z f64[N] (SoA, original atom order); verlet int32[N][M],
 //            dist f64[N][M], nn int32[N]   — rows in ORIGINAL atom order.
 //   scratch: cell_count u32[ncell] -> cell_start i32[ncell+1] (exclusive scan),
-//            rank i32[N] (slot handed out by the atomic bin counter),
+//            ent int2[N] ((cell, slot handed out by the cell's atomic counter) of every atom: k_assign -> k_scatter; afterwards
+//                           N ints of scratch for the in-cell sorts),
 //            order i32[N]  (atom ids sorted by cell; inside a cell DESCENDING id,
 //                           the order in which the reference's head-inserted
 //                           linked list is walked),
@@ -19,6 +20,7 @@
 #include "common.hpp"
 #include "grid.hpp"
 #include "cna_core.hpp"
+#include "assign_groups.hpp"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -40,13 +42,16 @@ int g_neighbor_variant = 0; // 0 = automatic, 1 = force the thread-per-atom kern
 // ----------------------------------------------------------------------------
 struct CellPlanes { int p0, p1, p2, p3; int *bad; }; // planes [p0, p1) and [p2, p3) of axis 0 hold every atom (bad == nullptr: not promised; else a pinned host word)
 // K atoms per lane: a wave takes 64 * K consecutive atoms as K slices of 64 (slice k: atom base + 64 k + lane, so adjacent lanes
-// still hold adjacent atoms and the runs below are found per slice).  The kernel is a chain of dependent memory trips — position
-// loads, the returning atomic, the stores — at full occupancy (26-34 VGPRs; 87 % of the wave-cycles waiting,
+// still hold adjacent atoms and the groups below are found per slice).  The kernel is a chain of dependent memory trips — position
+// loads, the returning atomic, the store — at full occupancy (26-38 VGPRs; 87 % of the wave-cycles waiting,
 // profiles/r05_step_counters.json): with K > 1 the loads of a lane's K atoms are in flight together, and so are its K atomics.
+// One atomic per group of lanes of a cell up to three lanes apart (assign_groups.hpp) and ONE 8-byte store of (cell, slot) per atom:
+// 133.8 -> 90-104 us at 10 M lattice atoms (8.23 M -> 6.73 M atomics, the distinct cells per slice; with runs of adjacent lanes and
+// two 4-byte stores before), profiles/assign_window.md.
 template <bool TRI, int K>
 __global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, const double *__restrict__ y,
                                                 const double *__restrict__ z, int64_t N, DBox b, Grid g,
-                                                int wrap_first, int *__restrict__ cell_id, int *__restrict__ rank,
+                                                int wrap_first, int2 *__restrict__ ent,
                                                 unsigned *__restrict__ cell_count, unsigned *__restrict__ ctl, unsigned gen,
                                                 double slack, unsigned short *__restrict__ mv, CellPlanes win,
                                                 CellGrid::Packed *__restrict__ rec, int drop_absent)
@@ -65,16 +70,13 @@ __global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, co
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int64_t i = i0 + 64 * k;
-        int cell = -1 - lane; // lanes past the end: distinct negative values, no run, no atomic
+        int cell = -1 - lane; // lanes past the end, absent atoms: negative, no group, no atomic
         // an atom whose x is NaN is ABSENT: it takes no cell, appears in nobody's row and gets no row of its own (the unused slots of a
         // decomposed system's fixed-size ghost block, slab.hip k_slab_append_static; the reference has no meaning for such input)
         // (only the neighbor builds — drop_absent — know what to do without such an atom: their kernels walk cells, and their per-atom
         // passes end at the number of atoms binned; every other user of the grid bins a NaN as it always did, into cell 0)
         const bool absent = drop_absent && i < N && xr[k] != xr[k];
-        if (absent) {
-            cell_id[i] = -1;
-            if (mv) mv[i] = (unsigned short)img::ATOM_NEUTRAL;
-        }
+        if (absent && mv) mv[i] = (unsigned short)img::ATOM_NEUTRAL;
         if (i < N && !absent) {
             double xi = xr[k], yi = yr[k], zi = zr[k];
             int code = img::ATOM_NEUTRAL; // (m + 15) per axis: raw = wrapped + m*L
@@ -112,34 +114,42 @@ __global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, co
                 outside = true;
                 cell = -1 - lane;
             }
-            cell_id[i] = cell;
         }
         cells[k] = cell;
     }
-    // One returning atomic per RUN of adjacent lanes in the same cell instead of one per atom: atoms usually arrive in some
-    // spatial order (a lattice builder, a file written cell by cell, a previous sort), so neighbouring lanes share cells;
-    // the slot inside a cell is arbitrary anyway (k_sort_cells restores the reference's order).  Unordered input pays a
-    // ballot and two shuffles.
+    // One returning atomic per GROUP of lanes in the same cell instead of one per atom: atoms usually arrive in some spatial
+    // order (a lattice builder, a file written cell by cell, a previous sort), so nearby lanes share cells; the slot inside a
+    // cell is arbitrary anyway (k_sort_cells restores the reference's order).  A group is a head and the lanes of its cell up
+    // to three behind it (assign_groups.hpp: the basis atoms of an fcc cell alternate between grid cells, A B A B), or, where
+    // that makes fewer atomics of the slice, a run of adjacent lanes.  Unordered input pays four shuffles (three up, one from the
+    // head) and seven ballots (primary heads, run starts, the two counts of atomics, the members at distance 1, 2, 3).
     unsigned base[K];
-    int first[K];
+    int head[K], slot[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) { // (the K atomics of the lane in flight together)
         const int cell = cells[k];
-        const int prev = __shfl_up(cell, 1, 64);
-        const bool head = lane == 0 || prev != cell || cell < 0;
-        const unsigned long long heads = __ballot(head);
-        first[k] = 63 - __builtin_clzll(heads & ((2ull << lane) - 1ull));                   // head of this lane's run
-        const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1));
-        const int last = later ? lane + __builtin_ctzll(later) : 63;                        // last lane of the run, as seen from its head
+        const int c1 = __shfl_up(cell, 1, 64);
+        const unsigned eq = assign_groups::equal_bits(cell, c1, __shfl_up(cell, 2, 64), __shfl_up(cell, 3, 64), lane);
+        const unsigned long long primary = __ballot(eq == 0);
+        int d = assign_groups::member_distance(eq, primary, lane);
+        const bool start = assign_groups::starts_run(cell, c1, lane);
+        const unsigned long long starts = __ballot(start);
+        int count;
+        if (assign_groups::use_runs(__popcll(__ballot(start && cell >= 0)), __popcll(__ballot(d == 0 && cell >= 0)))) // (wave-uniform)
+            d = assign_groups::run_distance(starts, lane, &count, &slot[k]);
+        else
+            assign_groups::count_and_rank(d, __ballot(d == 1), __ballot(d == 2), __ballot(d == 3), lane, &count, &slot[k]);
+        head[k] = lane - d;
         base[k] = 0;
-        if (head && cell >= 0)
-            base[k] = atomicAdd(&cell_count[cell], (unsigned)(last - lane + 1));
+        if (d == 0 && cell >= 0)
+            base[k] = atomicAdd(&cell_count[cell], (unsigned)count);
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const unsigned bs = __shfl(base[k], first[k], 64);
-        if (cells[k] >= 0)
-            rank[i0 + 64 * k] = (int)(bs + (unsigned)(lane - first[k]));
+        const unsigned bs = __shfl(base[k], head[k], 64);
+        const int64_t i = i0 + 64 * k;
+        if (i < N) // (cell < 0: absent, or outside a promised window — k_scatter leaves the atom out)
+            ent[i] = make_int2(cells[k], (int)(bs + (unsigned)slot[k]));
     }
     // what this kernel finds out about the input goes into generation-stamped control words (no memset per build): the scan
     // that follows turns them into the build's flags[0] (unwrapped input) and flags[4] (image codes present)
@@ -341,16 +351,22 @@ int exclusive_scan_u32(Scope &sc, const unsigned *in, int *out, int64_t n)
     return MDH_OK;
 }
 
-__global__ __launch_bounds__(256) void k_scatter(const int *__restrict__ cell_id, const int *__restrict__ rank,
-                                                 const int *__restrict__ cell_start, int *__restrict__ order,
-                                                 int64_t N)
+// ent: (cell, slot inside the cell) of every atom, one 8-byte entry from k_assign.  Two atoms per thread: their entries are ONE
+// 16-byte load: 31.9 us at 10 M atoms (8-byte loads run at 0.54-0.70 of the 16-byte rate: one atom per thread took 40.7 us, the two
+// separate arrays of ints before that 37.0; profiles/assign_window.md)
+__global__ __launch_bounds__(256) void k_scatter(const int2 *__restrict__ ent, const int *__restrict__ cell_start,
+                                                 int *__restrict__ order, int64_t N)
 {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= N)
         return;
-    const int c = cell_id[i];
-    if (c >= 0) // (< 0: an atom outside a promised cell window, k_assign)
-        order[cell_start[c] + rank[i]] = (int)i;
+    int4 e; // (ent is 256-byte aligned and i is even: the pair is 16-byte aligned)
+    if (i + 1 < N) e = *reinterpret_cast<const int4 *>(ent + i);
+    else { const int2 last = ent[i]; e = make_int4(last.x, last.y, -1, 0); }
+    if (e.x >= 0) // (< 0: an absent atom, or one outside a promised cell window, k_assign)
+        order[cell_start[e.x] + e.y] = (int)i;
+    if (e.z >= 0)
+        order[cell_start[e.z] + e.w] = (int)(i + 1);
 }
 
 // The atomic counters hand out slots in arbitrary order; put every cell's
@@ -396,7 +412,7 @@ __device__ __forceinline__ void sort_cell_net(int *__restrict__ order, int s, in
         if (u < n) order[s + u] = id[u];
 }
 
-// tmp: N ints of scratch indexed like `order` (the rank array of k_assign, free once the atoms are scattered), for cells of
+// tmp: N ints of scratch indexed like `order` (the entries of k_assign, free once the atoms are scattered), for cells of
 // more than eight atoms without a key: the ids are copied there and every atom is PLACED at the number of larger ids of its
 // cell — n^2 independent, cached reads instead of the insertion sort's chain of dependent ones (dense cells, rc = 5 A: 11 atoms
 // per cell, up to 50 in the fat last cells: 239 -> 204 us at 10 M atoms, 131 -> 94 us at 3.4 M)
@@ -461,7 +477,7 @@ __global__ __launch_bounds__(256) void k_sort_cells_dense(const int *__restrict_
     if (staged)
         for (int a = sub; a < n; a += 8) ids[lc * SORT_DENSE_CAP + a] = order[s + a];
     // a fuller cell — the LAST cell of an axis takes the remainder of the box (neighbor.cpp:58-61) and is up to twice as wide: the
-    // corner cell of a 256 k-atom box at rc = 5 A holds 84 atoms where the mean is 12 — goes through the free `rank` array instead,
+    // corner cell of a 256 k-atom box at rc = 5 A holds 84 atoms where the mean is 12 — goes through the free entries of k_assign instead,
     // still eight lanes to the cell (one lane, n * n loads: 330 us for that one cell, as long as the rest of the call)
     if (big)
         for (int a = sub; a < n; a += 8) tmp[s + a] = order[s + a];
@@ -680,8 +696,8 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
     unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
     cg.flags = sc.alloc_n<int>(8);
     cg.cell_start = sc.alloc_n<int>((size_t)g.ncell + 1);
-    int *cell_id = sc.alloc_n<int>((size_t)N);
-    int *rank = sc.alloc_n<int>((size_t)N);
+    int2 *ent = sc.alloc_n<int2>((size_t)N); // (cell, slot) of every atom: k_assign -> k_scatter
+    int *rank = reinterpret_cast<int *>(ent); // ... and, once the atoms are scattered, the N ints of scratch of the in-cell sorts
     cg.order = sc.alloc_n<int>((size_t)N + 4); // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
     unsigned short *mv = sc.alloc_n<unsigned short>((size_t)N);
     cg.xs = cg.ys = cg.zs = nullptr;
@@ -779,10 +795,10 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
     }
     const unsigned gen = next_scan_gen(); // stamps of this build's k_assign; the (first) scan below is launched with the same value
     // atoms per lane: four; small systems keep one atom per lane (they need the workgroups to fill the chip)
-    // (measured at 10 M atoms: 145 -> 120 us on a lattice, 162 -> 162 on a polycrystal — 10 M runs of one atom, the atomics' own
+    // (measured at 10 M atoms, with the grouping of round 5 — runs of adjacent lanes: 145 -> 120 us on a lattice, 162 -> 162 on a polycrystal — 10 M runs of one atom, the atomics' own
     // throughput — 413 -> 440 on a shuffled frame, which therefore keeps one: profiles/r05_assign_k.txt)
     const bool assign4 = N >= (int64_t)1 << 20 && !scattered;
-#define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)wrap_first, cell_id, rank, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
+#define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)wrap_first, ent, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
     if (b.tri) {
         if (assign4) MDH_ASSIGN(true, 4); else MDH_ASSIGN(true, 1);
     } else {
@@ -826,7 +842,7 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
         MDH_HIP(fill_err);
     }
     sc.keep_confirm(cell_count); // every counter a binned atom touched has been read and cleared by a scan enqueued above
-    hipLaunchKernelGGL(k_scatter, dim3(grid_for(N, 256)), dim3(256), 0, st, cell_id, rank, cg.cell_start, cg.order, N);
+    hipLaunchKernelGGL(k_scatter, dim3(grid_for((N + 1) / 2, 256)), dim3(256), 0, st, ent, cg.cell_start, cg.order, N);
     if (sort_desc) {
         if (!windowed && !sort_key && (double)N > 6.0 * (double)g.ncell) {
             hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rank);
@@ -1104,6 +1120,8 @@ __global__ __launch_bounds__(256) void k_neighbor_mop(SortedView sv, const int *
                                                       int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn, int64_t M,
                                                       int *__restrict__ max_count, TileFilter tf)
 {
+    if (tf.listed_sink && blockIdx.x == 0 && threadIdx.x == 0)
+        *tf.listed_sink = min(*tf.any, tf.list_cap); // (pinned host memory: the next build of this (N, grid) launches the slice pass if anything was listed)
     if (tf.moved && *tf.moved != 0) neighbor_atoms_body<TRI, MODE>(sv, cell_start, N, b, g, rc, verlet, dist, nn, M, max_count, tf);
     else neighbor_tiles_body<TRI, MODE>(sv, cell_start, b, g, rc, verlet, dist, nn, M, max_count, tf);
 }
@@ -1937,3 +1955,19 @@ int mdh_average_by_neighbor(double rc, const int *verlet, const double *dist, co
 }
 
 MDH_WARM_UNIT(neighbor)
+
+// the grouping rule of k_assign on the host (assign_groups.hpp), slice by slice
+extern "C" int64_t mdh_debug_assign_groups(const int *cells, int64_t n, int *head, int *count, int *rank)
+{
+    int64_t atomics = 0;
+    for (int64_t s0 = 0; s0 < n; s0 += 64) {
+        int c[64], h[64], k[64], r[64];
+        for (int l = 0; l < 64; ++l) c[l] = s0 + l < n ? cells[s0 + l] : -1 - l;
+        mdh::assign_groups::slice(c, h, k, r);
+        for (int l = 0; l < 64 && s0 + l < n; ++l) {
+            head[s0 + l] = h[l]; count[s0 + l] = k[l]; rank[s0 + l] = r[l];
+            atomics += k[l] > 0 && c[l] >= 0 ? 1 : 0;
+        }
+    }
+    return atomics;
+}

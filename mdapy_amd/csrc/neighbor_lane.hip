@@ -1434,9 +1434,11 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
     const float negc = -plan.mid;
     const int nt2b = nt[2] * nsub;
     // second pass: workgroups walk the listed tiles' slices.  Nothing was listed by the previous build with this (N, grid)
-    // (a lattice, nearly always): a small stand-by grid — it walks whatever turns up this time, slowly but correctly; 22 us of
-    // every build went into 1024 workgroups that found an empty list
-    const dim3 grid2(plan.last_listed == 0 ? 64u : 1024u);
+    // (a lattice, nearly always): no slice pass at all — the mop-up takes the first pass's own list, whatever turns up on it
+    // this time, slowly but correctly, and reports its length so that the next build launches the slice pass again (a
+    // stand-by launch that finds an empty list is 5 us and a kernel boundary of every build)
+    const bool slice_pass = plan.last_listed != 0;
+    const dim3 grid2(1024u);
     const Shape ts2 = make_shape(ts.txy, 1, nt[1], nt2b);
     const bool indirect = !cg.pk; // CellGrid::ix
     const lane::IndirectSrc isrc{cg.ix, cg.iy, cg.iz, cg.imv, cg.order};
@@ -1465,7 +1467,8 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
         } else {                                                                                                                          \
             MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, grid, 0, nt0_run, nt[1], nt[2], ts, nullptr, slot + ntiles, 0, max_count, flagged, nullptr, 0, 1, 2); \
         }                                                                                                                                 \
-        MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, grid2, 0, nt[0], nt[1], nt2b, ts2, nullptr, cg.flags + 2, 1, max_count, flagged2, flagged, nt[2], nsub, 3); \
+        if (slice_pass)                                                                                                                   \
+            MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, grid2, 0, nt[0], nt[1], nt2b, ts2, nullptr, cg.flags + 2, 1, max_count, flagged2, flagged, nt[2], nsub, 3); \
     } while (0)
     if (count) {
         if (plan.tk8) { if (b.tri) MDH_LANE_LAUNCH(true, true, false, true); else MDH_LANE_LAUNCH(true, false, false, true); }
@@ -1481,15 +1484,17 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
 #undef MDH_LANE_PASS_I
 #undef MDH_LANE_LAUNCH
     MDH_HIP(hipGetLastError());
-    // what the two passes listed for the thread-per-atom code (k_neighbor_tiles), in the tiling of the second pass
+    // what the passes listed for the thread-per-atom code (k_neighbor_mop): the slices of the second pass, or, without one, the
+    // tiles of the first in its own tiling
     tf.flag = reinterpret_cast<const unsigned char *>(flagged2); // (non-null: "a tiled kernel ran"; the per-tile byte flags are not used with a list)
-    tf.any = cg.flags + 3;
+    tf.any = cg.flags + (slice_pass ? 3 : 2);
     tf.moved = cg.flags;
-    tf.list = flagged2;
-    tf.list_cap = (int)std::min<int64_t>(ntiles * nsub, 2147483647);
-    tf.tile = ts2.txy;
-    tf.tile_z = ts2.tz;
-    tf.nt[0] = nt[0]; tf.nt[1] = nt[1]; tf.nt[2] = nt2b;
+    tf.list = slice_pass ? flagged2 : flagged;
+    tf.list_cap = (int)std::min<int64_t>(slice_pass ? ntiles * nsub : ntiles, 2147483647);
+    tf.tile = ts.txy;
+    tf.tile_z = slice_pass ? ts2.tz : ts.tz;
+    tf.nt[0] = nt[0]; tf.nt[1] = nt[1]; tf.nt[2] = slice_pass ? nt2b : nt[2];
+    tf.listed_sink = slice_pass ? nullptr : plan.listed_sink; // (the slice pass reports the first pass's count itself)
     return MDH_OK;
 }
 
