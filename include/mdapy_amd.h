@@ -88,7 +88,7 @@ int mdh_prof_enable(int on);
 int mdh_prof_reset(void);
 int mdh_prof_report(char *buf, int buflen);
 /* A/B switch for measurements and tests: 0 = automatic kernel choice (default), 1 = force the
- * thread-per-atom neighbor kernel, 2 = force the round-1 LDS-tiled kernel where it applies.  Results are identical. */
+ * thread-per-atom neighbor kernel, 2 (or any other value) = force the round-1 LDS-tiled kernel where it applies.  Results are identical. */
 int mdh_debug_set_neighbor_variant(int variant);
 /* A/B switch for measurements and tests: 1 (default; MDH_INDIRECT in the environment) = a neighbor build of input that comes in
  * some spatial order keeps no cell-sorted copy of the atoms, its kernels read them through the cell-sorted id list;

@@ -1,4 +1,4 @@
-// assign_groups.hpp — which lanes of a 64-atom slice share ONE returning atomic on their cell's counter (k_assign, neighbor.hip).
+// assign_groups.hpp — which lanes of a 64-atom slice share ONE returning atomic on their cell's counter (k_assign, cell_grid.hip).
 //
 // The rule, written once for the kernel and for the host (mdh_debug_assign_groups, tests/test_assign_groups.py).  It looks three
 // lanes back: the four basis atoms of an fcc lattice cell alternate between two or three grid cells (A B A B, not A A B B), so

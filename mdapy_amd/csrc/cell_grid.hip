@@ -1,0 +1,910 @@
+// cell_grid.hip — the cell grid of the cutoff neighbor search, kNN, RDF, Voronoi, the spatial sort and the overlap filter.
+//
+// Replaces build_cell of the reference (src/neighbor.cpp :64-100) and the cell arithmetic around it.
+//
+// Scratch in HBM:
+//   cell_count u32[ncell] -> cell_start i32[ncell+1] (exclusive scan),
+//   ent int2[N] ((cell, slot handed out by the cell's atomic counter) of every atom: k_assign -> k_scatter; afterwards
+//                  N ints of scratch for the in-cell sorts),
+//   order i32[N]  (atom ids sorted by cell; inside a cell DESCENDING id, the order in which the reference's head-inserted
+//                  linked list is walked),
+//   xs,ys,zs f64[N] (raw positions gathered into cell order, so a cell's atoms — and the 3 cells of a z-run — are
+//                  contiguous and loads are coalesced).
+#include "common.hpp"
+#include "grid.hpp"
+#include "assign_groups.hpp"
+#include <algorithm>
+#include <atomic>
+
+namespace mdh {
+// 1: neighbor builds of input in spatial order keep no sorted copy of the atoms (CellGrid::ix); 0: the 32-byte records always
+static std::atomic<int> g_indirect{[] { const char *e = std::getenv("MDH_INDIRECT"); return e ? std::atoi(e) : 1; }()};
+
+// ----------------------------------------------------------------------------
+// cell assignment: wrap, bin, take a slot from the cell's atomic counter
+// ----------------------------------------------------------------------------
+struct CellPlanes { int p0, p1, p2, p3; int *bad; }; // planes [p0, p1) and [p2, p3) of axis 0 hold every atom (bad == nullptr: not promised; else a pinned host word)
+// K atoms per lane: a wave takes 64 * K consecutive atoms as K slices of 64 (slice k: atom base + 64 k + lane, so adjacent lanes
+// still hold adjacent atoms and the groups below are found per slice).  The kernel is a chain of dependent memory trips — position
+// loads, the returning atomic, the store — at full occupancy (26-38 VGPRs; 87 % of the wave-cycles waiting,
+// profiles/r05_step_counters.json): with K > 1 the loads of a lane's K atoms are in flight together, and so are its K atomics.
+// One atomic per group of lanes of a cell up to three lanes apart (assign_groups.hpp) and ONE 8-byte store of (cell, slot) per atom:
+// 133.8 -> 90-104 us at 10 M lattice atoms (8.23 M -> 6.73 M atomics, the distinct cells per slice; with runs of adjacent lanes and
+// two 4-byte stores before), profiles/assign_window.md.
+template <bool TRI, int K>
+__global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, const double *__restrict__ y,
+                                                const double *__restrict__ z, int64_t N, DBox b, Grid g,
+                                                int wrap_first, int2 *__restrict__ ent,
+                                                unsigned *__restrict__ cell_count, unsigned *__restrict__ ctl, unsigned gen,
+                                                double slack, unsigned short *__restrict__ mv, CellPlanes win,
+                                                CellGrid::Packed *__restrict__ rec, int drop_absent)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * (64 * K) + lane;
+    bool moved = false, outside = false, coded = false;
+    double xr[K], yr[K], zr[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { // (all loads of the lane first)
+        const int64_t i = i0 + 64 * k;
+        xr[k] = yr[k] = zr[k] = 0.0;
+        if (i < N) { xr[k] = x[i]; yr[k] = y[i]; zr[k] = z[i]; }
+    }
+    int cells[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int64_t i = i0 + 64 * k;
+        int cell = -1 - lane; // lanes past the end, absent atoms: negative, no group, no atomic
+        // an atom whose x is NaN is ABSENT: it takes no cell, appears in nobody's row and gets no row of its own (the unused slots of a
+        // decomposed system's fixed-size ghost block, slab.hip k_slab_append_static; the reference has no meaning for such input)
+        // (only the neighbor builds — drop_absent — know what to do without such an atom: their kernels walk cells, and their per-atom
+        // passes end at the number of atoms binned; every other user of the grid bins a NaN as it always did, into cell 0)
+        const bool absent = drop_absent && i < N && xr[k] != xr[k];
+        if (absent && mv) mv[i] = (unsigned short)img::ATOM_NEUTRAL;
+        if (i < N && !absent) {
+            double xi = xr[k], yi = yr[k], zi = zr[k];
+            int code = img::ATOM_NEUTRAL; // (m + 15) per axis: raw = wrapped + m*L
+            if (wrap_first && b.anypbc) { // neighbor.cpp:88-91
+                wrap<TRI>(b, xi, yi, zi);
+                if (!TRI) {
+                    // whole box lengths between the raw and the wrapped coordinate (an unwrapped trajectory: a few); more than
+                    // img::MAX_M of them, or a coordinate that is not wrapped + m L to within `slack`, invalidates the image codes
+                    // for this call (flags[0])
+                    const double raw[3] = {xr[k], yr[k], zr[k]}, wrp[3] = {xi, yi, zi};
+                    code = 0;
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        double m = 0.0;
+                        if (b.pbc[d] && raw[d] != wrp[d]) { // already wrapped (the common case): m = 0, no division
+                            m = rint((raw[d] - wrp[d]) / b.h[d * 4]);
+                            if (!(fabs(m) <= (double)img::MAX_M) || !(fabs(raw[d] - m * b.h[d * 4] - wrp[d]) <= slack)) { moved = true; m = 0.0; }
+                        }
+                        code |= ((int)m + 15) << (5 * d);
+                    }
+                }
+            }
+            if (mv) mv[i] = (unsigned short)code;
+            // scattered input (mdh_spatial_sort): the atom as ONE 32-byte record in input order — the gather then reads one random
+            // sector per atom instead of three (x, y, z) or four (the image code)
+            if (rec) rec[i] = CellGrid::Packed{xr[k], yr[k], zr[k], (int)i, code};
+            coded = coded || code != img::ATOM_NEUTRAL;
+            int c0, c1, c2;
+            cell_coords<TRI>(b, g, xi, yi, zi, c0, c1, c2);
+            cell = (c0 * g.nc[1] + c1) * g.nc[2] + c2; // neighbor.cpp:24-27 (ncell < 2^31 checked on the host)
+            if (win.bad && !((c0 >= win.p0 && c0 < win.p1) || (c0 >= win.p2 && c0 < win.p3))) {
+                // an atom outside the window of planes the caller promised (mdh_hint_cell_window): the counters out there were
+                // never zeroed — it takes no slot and is not scattered (cell -1); the build is reported broken (win.bad), its
+                // rows are not to be used, and nothing is written out of bounds
+                outside = true;
+                cell = -1 - lane;
+            }
+        }
+        cells[k] = cell;
+    }
+    // One returning atomic per GROUP of lanes in the same cell instead of one per atom: atoms usually arrive in some spatial
+    // order (a lattice builder, a file written cell by cell, a previous sort), so nearby lanes share cells; the slot inside a
+    // cell is arbitrary anyway (k_sort_cells restores the reference's order).  A group is a head and the lanes of its cell up
+    // to three behind it (assign_groups.hpp: the basis atoms of an fcc cell alternate between grid cells, A B A B), or, where
+    // that makes fewer atomics of the slice, a run of adjacent lanes.  Unordered input pays four shuffles (three up, one from the
+    // head) and seven ballots (primary heads, run starts, the two counts of atomics, the members at distance 1, 2, 3).
+    unsigned base[K];
+    int head[K], slot[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { // (the K atomics of the lane in flight together)
+        const int cell = cells[k];
+        const int c1 = __shfl_up(cell, 1, 64);
+        const unsigned eq = assign_groups::equal_bits(cell, c1, __shfl_up(cell, 2, 64), __shfl_up(cell, 3, 64), lane);
+        const unsigned long long primary = __ballot(eq == 0);
+        int d = assign_groups::member_distance(eq, primary, lane);
+        const bool start = assign_groups::starts_run(cell, c1, lane);
+        const unsigned long long starts = __ballot(start);
+        int count;
+        if (assign_groups::use_runs(__popcll(__ballot(start && cell >= 0)), __popcll(__ballot(d == 0 && cell >= 0)))) // (wave-uniform)
+            d = assign_groups::run_distance(starts, lane, &count, &slot[k]);
+        else
+            assign_groups::count_and_rank(d, __ballot(d == 1), __ballot(d == 2), __ballot(d == 3), lane, &count, &slot[k]);
+        head[k] = lane - d;
+        base[k] = 0;
+        if (d == 0 && cell >= 0)
+            base[k] = atomicAdd(&cell_count[cell], (unsigned)count);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const unsigned bs = __shfl(base[k], head[k], 64);
+        const int64_t i = i0 + 64 * k;
+        if (i < N) // (cell < 0: absent, or outside a promised window — k_scatter leaves the atom out)
+            ent[i] = make_int2(cells[k], (int)(bs + (unsigned)slot[k]));
+    }
+    // what this kernel finds out about the input goes into generation-stamped control words (no memset per build): the scan
+    // that follows turns them into the build's flags[0] (unwrapped input) and flags[4] (image codes present)
+    if (__any(moved) && lane == 0)
+        ctl[1] = gen;
+    if (__any(coded) && lane == 0)
+        ctl[2] = gen; // some atom was handed in outside the box: the gather has to read the image codes (else they are all neutral)
+    if (__any(outside) && lane == 0)
+        *win.bad = 1; // (pinned host memory: read by the next build of the thread / mdh_cell_window_check)
+}
+
+// ----------------------------------------------------------------------------
+// exclusive prefix sum of the bin counters (three small kernels)
+// ----------------------------------------------------------------------------
+static constexpr int SCAN_BLOCK = 256;
+static constexpr int SCAN_ITEMS = 4; // per thread -> 1024 per block (small inputs); SCAN_ITEMS_BIG for large ones
+static constexpr int SCAN_ITEMS_BIG = 32; // 8192 per block: every block takes a ticket from ONE word, ~90 of them per microsecond —
+                                          // with 1024 per block the 3 925 tickets of a 4 M-cell grid were 43 of the scan's 62 us
+static constexpr int64_t SCAN_BIG_FROM = 1 << 19; // items from which the big blocks are used
+
+__device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        unsigned t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// block-wide exclusive scan of one value per thread (256 threads = 4 waves); returns exclusive prefix, total via *tot
+__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *tot)
+{
+    __shared__ unsigned wsum[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned inc = wave_incl_scan(v, lane);
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    unsigned off = 0, t = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < w) off += wsum[k];
+        t += wsum[k];
+    }
+    __syncthreads();
+    *tot = t;
+    return off + inc - v;
+}
+
+// ----------------------------------------------------------------------------
+// Single-pass exclusive scan (decoupled look-back: Merrill & Garland, "Single-pass parallel prefix scan with decoupled
+// look-back", NVIDIA NVR-2016-002) — ONE launch instead of three: at a few thousand atoms a build is a chain of dependent
+// launches of ~4 us each, whatever they do.  A block takes a ticket (so that every predecessor it waits for is already
+// running), scans its 1024 items, publishes its total, and wave 0 collects the totals / inclusive prefixes of the blocks
+// before it, 64 at a time.  Control words live in a kept block (Scope::KEEP_SCAN): ctl[0] the ticket counter (reset by
+// the block that takes the last ticket), ctl[1], ctl[2] the stamps of k_assign, status words from byte 256 on:
+// generation (30 bits) | state (2: 1 = block total, 2 = inclusive prefix) | value (32) — a word of an earlier launch
+// carries an older generation and reads as "not there yet", so nothing is cleared between launches.
+// REZERO: the input is a build's bin counters in a KEEP_ZERO block: every counter is cleared as it is read.
+// flags != nullptr: the first block also writes the build's eight device flags (grid.hpp) from the stamps.
+// ----------------------------------------------------------------------------
+static std::atomic<unsigned> g_scan_gen{0};
+static unsigned next_scan_gen()
+{
+    unsigned g = (++g_scan_gen) & 0x3fffffffu;
+    if (g == 0) { // 2^30 launches: old status words could repeat a generation — start over from clean control blocks
+        reset_kept_blocks(Scope::KEEP_SCAN);
+        g = (++g_scan_gen) & 0x3fffffffu;
+    }
+    return g;
+}
+
+template <bool REZERO, int ITEMS = SCAN_ITEMS>
+__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_onepass(unsigned *__restrict__ in, int *__restrict__ out, int64_t n,
+                                                             unsigned *__restrict__ ctl, unsigned gen, int *__restrict__ flags)
+{
+    constexpr int SCAN_ITEMS = ITEMS; // (shadows the namespace constant: the body below is written for any multiple of four)
+    __shared__ unsigned s_blk, s_excl;
+    unsigned long long *status = reinterpret_cast<unsigned long long *>(ctl + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) s_blk = atomicAdd(&ctl[0], 1u);
+    __syncthreads();
+    const unsigned blk = s_blk, nblk = gridDim.x;
+    if (tid == 0) {
+        if (blk == nblk - 1) ctl[0] = 0; // every ticket has been taken: ready for the next launch
+        if (blk == 0 && flags) {
+            flags[0] = ctl[1] == gen ? 1 : 0; flags[1] = 0; flags[2] = 0; flags[3] = 0;
+            flags[4] = ctl[2] == gen ? 1 : 0; flags[5] = 0; flags[6] = 0; flags[7] = 0;
+        }
+    }
+    const int64_t base = ((int64_t)blk * SCAN_BLOCK + tid) * SCAN_ITEMS;
+    unsigned v[SCAN_ITEMS], s = 0;
+    const bool vec = base + SCAN_ITEMS <= n && ((reinterpret_cast<uintptr_t>(in + base) | reinterpret_cast<uintptr_t>(out + base)) & 15u) == 0;
+    if (vec) {
+#pragma unroll
+        for (int c = 0; c < SCAN_ITEMS / 4; ++c) {
+            const uint4 q = reinterpret_cast<const uint4 *>(in + base)[c];
+            v[4 * c] = q.x; v[4 * c + 1] = q.y; v[4 * c + 2] = q.z; v[4 * c + 3] = q.w;
+        }
+        if (REZERO) {
+#pragma unroll
+            for (int c = 0; c < SCAN_ITEMS / 4; ++c) reinterpret_cast<uint4 *>(in + base)[c] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            v[k] = (base + k < n) ? in[base + k] : 0u;
+            if (REZERO && base + k < n) in[base + k] = 0u;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) s += v[k];
+    unsigned tot;
+    unsigned ex = block_excl_scan(s, &tot);
+    const unsigned long long stamp = (unsigned long long)gen << 34;
+    if (tid == 0) // this block's total (block 0: its inclusive prefix) for the blocks behind it
+        __hip_atomic_store(&status[blk], stamp | ((unsigned long long)(blk == 0 ? 2u : 1u) << 32) | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < 64) {
+        unsigned excl = 0;
+        if (blk > 0) {
+            int64_t j = (int64_t)blk - 1; // nearest predecessor
+            for (;;) {
+                const int64_t idx = j - lane;
+                unsigned long long st;
+                for (;;) {
+                    st = idx >= 0 ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (stamp | (2ull << 32));
+                    const bool there = (st >> 34) == gen && ((st >> 32) & 3u) != 0;
+                    if (__all(there))
+                        break;
+                    __builtin_amdgcn_s_sleep(2);
+                }
+                const unsigned long long pm = __ballot(((st >> 32) & 3u) == 2u);
+                const int first = pm ? __builtin_ctzll(pm) : 64; // nearest block that already knows its inclusive prefix
+                unsigned val = lane <= first ? (unsigned)(st & 0xffffffffull) : 0u;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) val += __shfl_xor(val, d, 64);
+                excl += val;
+                if (pm)
+                    break;
+                j -= 64;
+            }
+            if (lane == 0)
+                __hip_atomic_store(&status[blk], stamp | (2ull << 32) | (unsigned long long)(excl + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (lane == 0) s_excl = excl;
+    }
+    __syncthreads();
+    ex += s_excl;
+    if (vec) {
+#pragma unroll
+        for (int c = 0; c < SCAN_ITEMS / 4; ++c) {
+            int4 o;
+            o.x = (int)ex; o.y = (int)(ex + v[4 * c]); o.z = (int)(ex + v[4 * c] + v[4 * c + 1]); o.w = (int)(ex + v[4 * c] + v[4 * c + 1] + v[4 * c + 2]);
+            reinterpret_cast<int4 *>(out + base)[c] = o;
+            ex += v[4 * c] + v[4 * c + 1] + v[4 * c + 2] + v[4 * c + 3];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            if (base + k < n) out[base + k] = (int)ex;
+            ex += v[k];
+        }
+    }
+    if (blk == nblk - 1 && tid == 0) out[n] = (int)(s_excl + tot); // grand total
+}
+
+static size_t scan_ctl_bytes(int64_t n)
+{
+    const int64_t per = (int64_t)SCAN_BLOCK * SCAN_ITEMS;
+    return 256 + (size_t)((n + per - 1) / per) * 8;
+}
+// out[0..n] = exclusive prefix of in[0..n), out[n] = total; rezero: clear in[] on the way (bin counters of a kept block)
+static void launch_scan_gen(hipStream_t st, unsigned *in, int *out, int64_t n, unsigned *ctl, unsigned gen, bool rezero, int *flags)
+{
+    const bool big = n >= SCAN_BIG_FROM;
+    const int64_t per = (int64_t)SCAN_BLOCK * (big ? SCAN_ITEMS_BIG : SCAN_ITEMS);
+    const dim3 grid((unsigned)std::max<int64_t>(1, (n + per - 1) / per)), block(SCAN_BLOCK);
+    if (big) {
+        if (rezero) hipLaunchKernelGGL((k_scan_onepass<true, SCAN_ITEMS_BIG>), grid, block, 0, st, in, out, n, ctl, gen, flags);
+        else hipLaunchKernelGGL((k_scan_onepass<false, SCAN_ITEMS_BIG>), grid, block, 0, st, in, out, n, ctl, gen, flags);
+    } else {
+        if (rezero) hipLaunchKernelGGL((k_scan_onepass<true, SCAN_ITEMS>), grid, block, 0, st, in, out, n, ctl, gen, flags);
+        else hipLaunchKernelGGL((k_scan_onepass<false, SCAN_ITEMS>), grid, block, 0, st, in, out, n, ctl, gen, flags);
+    }
+}
+static void launch_scan(hipStream_t st, unsigned *in, int *out, int64_t n, unsigned *ctl, bool rezero, int *flags)
+{
+    launch_scan_gen(st, in, out, n, ctl, next_scan_gen(), rezero, flags);
+}
+
+// out[0..n] = exclusive prefix sums of in[0..n) (out[n] = total); for other translation units (grid.hpp)
+int exclusive_scan_u32(Scope &sc, const unsigned *in, int *out, int64_t n)
+{
+    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(n), Scope::KEEP_SCAN));
+    if (sc.failed())
+        return sc.error();
+    launch_scan(sc.stream(), const_cast<unsigned *>(in), out, n, ctl, false, nullptr);
+    MDH_HIP(hipGetLastError());
+    return MDH_OK;
+}
+
+// ent: (cell, slot inside the cell) of every atom, one 8-byte entry from k_assign.  Two atoms per thread: their entries are ONE
+// 16-byte load: 31.9 us at 10 M atoms (8-byte loads run at 0.54-0.70 of the 16-byte rate: one atom per thread took 40.7 us, the two
+// separate arrays of ints before that 37.0; profiles/assign_window.md)
+__global__ __launch_bounds__(256) void k_scatter(const int2 *__restrict__ ent, const int *__restrict__ cell_start,
+                                                 int *__restrict__ order, int64_t N)
+{
+    const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= N)
+        return;
+    int4 e; // (ent is 256-byte aligned and i is even: the pair is 16-byte aligned)
+    if (i + 1 < N) e = *reinterpret_cast<const int4 *>(ent + i);
+    else { const int2 last = ent[i]; e = make_int4(last.x, last.y, -1, 0); }
+    if (e.x >= 0) // (< 0: an absent atom, or one outside a promised cell window, k_assign)
+        order[cell_start[e.x] + e.y] = (int)i;
+    if (e.z >= 0)
+        order[cell_start[e.z] + e.w] = (int)(i + 1);
+}
+
+// The atomic counters hand out slots in arbitrary order; put every cell's
+// atoms into DESCENDING id order (what a walk of the reference's linked list
+// sees, neighbor.cpp:97-98) so that rows come out in reference order and the
+// result is deterministic.  One thread per cell; cells hold a handful of atoms.
+// key != nullptr: descending key[id] instead of descending id (a decomposed system: key = global atom id, so that the rows of
+// a slab come out in the order the whole system's rows have)
+// Cells of up to eight atoms (nearly all of them at cell width rc) are sorted in registers: the ids, then the keys, loaded as
+// one batch, a sorting network with fixed indices, the ids stored back.  The insertion sort below — every comparison a
+// dependent read of order[] and, with a key, of key[order[]] — was a chain of 6-10 memory latencies per cell: 32 us of the
+// headline build, 77 us of a slab's (random 8-byte key reads).
+template <int W, typename K>
+__device__ __forceinline__ void sort_cell_net(int *__restrict__ order, int s, int n, const int64_t *__restrict__ key)
+{
+    int id[W];
+    K k[W];
+#pragma unroll
+    for (int u = 0; u < W; ++u) id[u] = order[s + min(u, n - 1)];
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+        const K v = key ? (K)key[id[u]] : (K)id[u];
+        k[u] = u < n ? v : (sizeof(K) == 8 ? (K)INT64_MIN : (K)INT32_MIN); // pads sink to the end (descending order)
+    }
+    auto ce = [&](int a, int b) { // k[a] >= k[b] afterwards
+        const bool sw = k[a] < k[b];
+        const K ka = sw ? k[b] : k[a], kb = sw ? k[a] : k[b];
+        const int ia = sw ? id[b] : id[a], ib = sw ? id[a] : id[b];
+        k[a] = ka; k[b] = kb; id[a] = ia; id[b] = ib;
+    };
+    if (W == 4) {
+        ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2);
+    } else { // Batcher's odd-even merge sort of eight
+        ce(0, 1); ce(2, 3); ce(4, 5); ce(6, 7);
+        ce(0, 2); ce(1, 3); ce(4, 6); ce(5, 7);
+        ce(1, 2); ce(5, 6);
+        ce(0, 4); ce(1, 5); ce(2, 6); ce(3, 7);
+        ce(2, 4); ce(3, 5);
+        ce(1, 2); ce(3, 4); ce(5, 6);
+    }
+#pragma unroll
+    for (int u = 0; u < W; ++u)
+        if (u < n) order[s + u] = id[u];
+}
+
+// tmp: N ints of scratch indexed like `order` (the entries of k_assign, free once the atoms are scattered), for cells of
+// more than eight atoms without a key: the ids are copied there and every atom is PLACED at the number of larger ids of its
+// cell — n^2 independent, cached reads instead of the insertion sort's chain of dependent ones (dense cells, rc = 5 A: 11 atoms
+// per cell, up to 50 in the fat last cells: 239 -> 204 us at 10 M atoms, 131 -> 94 us at 3.4 M)
+__global__ __launch_bounds__(256) void k_sort_cells(const int *__restrict__ cell_start, int *__restrict__ order,
+                                                    int64_t ncell, const int64_t *__restrict__ key, int *__restrict__ tmp)
+{
+    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncell)
+        return;
+    const int s = cell_start[c], e = cell_start[c + 1];
+    const int n = e - s;
+    if (n <= 1)
+        return;
+    if (n <= 4) {
+        if (key) sort_cell_net<4, int64_t>(order, s, n, key);
+        else sort_cell_net<4, int>(order, s, n, nullptr);
+        return;
+    }
+    if (n <= 8) {
+        if (key) sort_cell_net<8, int64_t>(order, s, n, key);
+        else sort_cell_net<8, int>(order, s, n, nullptr);
+        return;
+    }
+    if (!key && tmp) {
+        for (int a = s; a < e; ++a) tmp[a] = order[a];
+        for (int a = s; a < e; ++a) {
+            const int mine = tmp[a];
+            int larger = 0;
+            for (int q = s; q < e; ++q) larger += tmp[q] > mine ? 1 : 0;
+            order[s + larger] = mine; // (ids are distinct: every slot of the cell is written once)
+        }
+        return;
+    }
+    for (int a = s + 1; a < e; ++a) {
+        int v = order[a], q = a - 1;
+        const int64_t kv = key ? key[v] : (int64_t)v;
+        while (q >= s && (key ? key[order[q]] : (int64_t)order[q]) < kv) {
+            order[q + 1] = order[q];
+            --q;
+        }
+        order[q + 1] = v;
+    }
+}
+
+// The same order for grids of many atoms per cell (N / ncell > 6: rc = 5 A in a metal, 11 atoms per cell): EIGHT lanes per cell.
+// The cell's ids are staged in LDS (64 per cell; a fuller cell is sorted by its first lane as above), then lane l
+// ranks the atoms l, l + 8, ... by counting the larger ids of its cell — n / 8 trips of n LDS reads instead of n * n dependent
+// global ones in a single lane (rc = 6 A, 18 atoms per cell, 4 M atoms: 240 us, as long as k_assign, k_scatter and k_gather together).
+constexpr int SORT_DENSE_CAP = 64;
+__global__ __launch_bounds__(256) void k_sort_cells_dense(const int *__restrict__ cell_start, int *__restrict__ order, int64_t ncell,
+                                                          int *__restrict__ tmp)
+{
+    __shared__ int ids[32 * SORT_DENSE_CAP];
+    const int sub = threadIdx.x & 7, lc = threadIdx.x >> 3;
+    const int64_t c = (int64_t)blockIdx.x * 32 + lc;
+    int s = 0, n = 0;
+    if (c < ncell) {
+        s = cell_start[c];
+        n = cell_start[c + 1] - s;
+    }
+    const bool staged = n > 1 && n <= SORT_DENSE_CAP, big = n > SORT_DENSE_CAP;
+    if (staged)
+        for (int a = sub; a < n; a += 8) ids[lc * SORT_DENSE_CAP + a] = order[s + a];
+    // a fuller cell — the LAST cell of an axis takes the remainder of the box (neighbor.cpp:58-61) and is up to twice as wide: the
+    // corner cell of a 256 k-atom box at rc = 5 A holds 84 atoms where the mean is 12 — goes through the free entries of k_assign instead,
+    // still eight lanes to the cell (one lane, n * n loads: 330 us for that one cell, as long as the rest of the call)
+    if (big)
+        for (int a = sub; a < n; a += 8) tmp[s + a] = order[s + a];
+    __syncthreads(); // (workgroup scope: the copies in LDS and in HBM are visible to the cell's other lanes)
+    if (staged) {
+        for (int a = sub; a < n; a += 8) {
+            const int mine = ids[lc * SORT_DENSE_CAP + a];
+            int larger = 0;
+            for (int q = 0; q < n; ++q) larger += ids[lc * SORT_DENSE_CAP + q] > mine ? 1 : 0;
+            order[s + larger] = mine; // (ids are distinct: every slot of the cell is written once)
+        }
+    } else if (big) {
+        for (int a = sub; a < n; a += 8) {
+            const int mine = tmp[s + a];
+            int larger = 0;
+            for (int q = 0; q < n; ++q) larger += tmp[s + q] > mine ? 1 : 0;
+            order[s + larger] = mine;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gather(const double *__restrict__ x, const double *__restrict__ y,
+                                                const double *__restrict__ z, const int *__restrict__ order,
+                                                double *__restrict__ xs, double *__restrict__ ys,
+                                                double *__restrict__ zs, int64_t N,
+                                                const unsigned short *__restrict__ mv, unsigned short *__restrict__ mvs,
+                                                CellGrid::Packed *__restrict__ pk, const int *__restrict__ any_code,
+                                                const int *__restrict__ n_binned)
+{
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N)
+        return;
+    if (n_binned && p >= *n_binned) // a windowed build that dropped atoms outside its window: order[] ends at the atoms binned
+        return;
+    const int i = order[p];
+
+    const double a = x[i], b = y[i], c = z[i];
+    // the image codes are a fourth scattered read per atom (one byte each); k_assign says whether any of them is not neutral
+    const unsigned short m = *any_code ? mv[i] : (unsigned short)img::ATOM_NEUTRAL;
+    if (pk) {
+        pk[p] = CellGrid::Packed{a, b, c, i, (int)m};
+        return;
+    }
+    xs[p] = a;
+    ys[p] = b;
+    zs[p] = c;
+    mvs[p] = m;
+}
+
+// the gather of scattered input: whole records (written in input order by k_assign), one random 32-byte read per atom
+__global__ __launch_bounds__(256) void k_gather_records(const CellGrid::Packed *__restrict__ rec, const int *__restrict__ order,
+                                                        CellGrid::Packed *__restrict__ pk, int64_t N, const int *__restrict__ n_binned)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N || p >= *n_binned)
+        return;
+    pk[p] = rec[order[p]];
+}
+
+__global__ __launch_bounds__(256) void k_unpack(const CellGrid::Packed *__restrict__ pk, int64_t N, double *__restrict__ xs,
+                                                double *__restrict__ ys, double *__restrict__ zs, unsigned short *__restrict__ mvs)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N)
+        return;
+    const CellGrid::Packed r = pk[p];
+    xs[p] = r.x; ys[p] = r.y; zs[p] = r.z; mvs[p] = (unsigned short)r.code;
+}
+
+int ensure_unpacked(Scope &sc, CellGrid &cg, int64_t N)
+{
+    if ((!cg.pk && !cg.ix) || cg.xs)
+        return MDH_OK;
+    cg.xs = sc.alloc_n<double>((size_t)N);
+    cg.ys = sc.alloc_n<double>((size_t)N);
+    cg.zs = sc.alloc_n<double>((size_t)N);
+    cg.mvs = sc.alloc_n<unsigned short>((size_t)N);
+    if (sc.failed())
+        return sc.error();
+    if (cg.pk) // from the records
+        hipLaunchKernelGGL(k_unpack, dim3(grid_for(N, 256)), dim3(256), 0, sc.stream(), cg.pk, N, cg.xs, cg.ys, cg.zs, cg.mvs);
+    else // an indirect grid: the gather its build left out
+        hipLaunchKernelGGL(k_gather, dim3(grid_for(N, 256)), dim3(256), 0, sc.stream(), cg.ix, cg.iy, cg.iz, cg.order, cg.xs, cg.ys, cg.zs, N, cg.imv,
+                           cg.mvs, (CellGrid::Packed *)nullptr, cg.flags + 4, cg.cell_start + cg.g.ncell);
+    MDH_HIP(hipGetLastError());
+    return MDH_OK;
+}
+
+// ----------------------------------------------------------------------------
+// Cell window (decomposed systems).  A rank's atoms — its slab and the halo — occupy a few planes of the GLOBAL cell grid the
+// neighbor build works on (global box, global cells: the rows equal the undivided system's), and the passes over ALL cells
+// (bin counters zeroed, three scan kernels, the in-cell sort) then cost more than the passes over the atoms.  The caller, who
+// knows where its atoms are, promises a window of fractional coordinates along one axis (mdh_hint_cell_window, consumed by
+// the next build on this thread); those passes run over the window's planes (one more on each side) only, and the prefix
+// array outside them is filled with the constants a full scan would have left there, so that every reader of cell_start is
+// served as before.  An atom binned outside the promised window breaks the promise: counted on the device, reported by
+// the next call of this thread that builds a grid.
+// ----------------------------------------------------------------------------
+struct CellWindow { int axis = 0; double lo = 0.0, hi = 0.0; bool set = false; };
+// The hints for the NEXT grid build of this thread: the window, and inside it the stretch that holds the atoms whose rows are wanted
+// (mdh_hint_centre_window: a rank's OWN slab; what lies between it and the window's ends are ghosts — candidates of the tile
+// kernel, never its centres: their rows are not made)
+struct PendingWindows { CellWindow cells, centre; };
+static thread_local PendingWindows g_pending;
+static thread_local int *g_window_violations = nullptr; // pinned host word of the previous windowed build
+
+// The top of every grid build: the thread's hints are taken (and with that spent, whatever the build is for), and a promise the
+// previous windowed build found broken is reported
+static int take_pending_windows(PendingWindows &w)
+{
+    w = g_pending;
+    g_pending = PendingWindows{};
+    if (g_window_violations && *(volatile int *)g_window_violations != 0) {
+        *g_window_violations = 0;
+        set_error("an earlier neighbor build on this thread found atoms outside the cell window it had been promised (mdh_hint_cell_window)");
+        return MDH_ERR_ARG;
+    }
+    return MDH_OK;
+}
+
+// out[a..b) = *v (a value that is on the device only)
+// (16-byte stores over the aligned middle — the region behind a slab's window is most of the global grid, 100 MB on eight ranks —
+// launched by fill_from() below)
+__global__ __launch_bounds__(256) void k_fill_from(int *__restrict__ out, int64_t a, int64_t b, const int *__restrict__ v)
+{
+    const int val = *v;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b - a < 8) {
+        if (a + i < b) out[a + i] = val;
+        return;
+    }
+    const int64_t a4 = (a + 3) & ~(int64_t)3, b4 = b & ~(int64_t)3; // a4 <= b4: out is 16-byte aligned at multiples of four
+    const int64_t q = a4 + 4 * i;
+    if (q + 4 <= b4) *reinterpret_cast<int4 *>(out + q) = make_int4(val, val, val, val);
+    if (i < 4) {
+        if (a + i < a4) out[a + i] = val;
+        if (b4 + i < b) out[b4 + i] = val;
+    }
+}
+// a one-piece window [a0, a1] of the grid: zeros in front of it, *v (the atoms binned, cell_start[a1]) behind it — ONE launch behind
+// the window's scan instead of a memset in front of it and a fill behind (a memset is two 5 us nodes on the stream)
+__global__ __launch_bounds__(256) void k_fill_outside(int *__restrict__ out, int64_t a0, int64_t a1, int64_t n1, const int *__restrict__ v)
+{
+    const int val = *v;
+    const int64_t q = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    const int64_t head4 = (a0 + 3) >> 2 << 2;               // the head [0, a0) rounded up to whole quads (the overshoot is fixed below)
+    const int64_t t0 = (a1 + 1 + 3) & ~(int64_t)3;          // first aligned index behind the window
+    if (q < head4) {
+        if (q + 4 <= a0) *reinterpret_cast<int4 *>(out + q) = make_int4(0, 0, 0, 0);
+        else for (int64_t i = q; i < a0; ++i) out[i] = 0;
+        return;
+    }
+    const int64_t r = q - head4 + t0;                       // quads behind the window
+    if (r == t0) for (int64_t i = a1 + 1; i < t0 && i < n1; ++i) out[i] = val;
+    if (r + 4 <= n1) *reinterpret_cast<int4 *>(out + r) = make_int4(val, val, val, val);
+    else for (int64_t i = r; i < n1; ++i) out[i] = val;
+}
+static void fill_from(hipStream_t st, int *out, int64_t a, int64_t b, const int *v)
+{
+    if (b > a)
+        hipLaunchKernelGGL(k_fill_from, dim3(grid_for((b - a) / 4 + 8, 256)), dim3(256), 0, st, out, a, b, v);
+}
+
+// out[a..b) += *v  (v outside [a, b)); the entry `skip`, if in range, is left alone
+__global__ __launch_bounds__(256) void k_add_from(int *__restrict__ out, int64_t a, int64_t b, const int *__restrict__ v, int64_t skip)
+{
+    const int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < b && i != skip) out[i] += *v;
+}
+
+// atoms binned outside planes [p0, p1) u [p2, p3) of axis 0 (cells are a0-major)
+int neighbor_grid_dims(const DBox &b, double rc, Grid &g)
+{
+    double nc_total = 1.0;
+    for (int d = 0; d < 3; ++d) { // neighbor.cpp:203-206
+        double f = std::floor(b.thick[d] / rc);
+        if (!(f < 2147483647.0)) { set_error("cell grid too large (box thickness / rc overflows int)"); return MDH_ERR_ARG; }
+        int n = (int)f;
+        g.nc[d] = n > 3 ? n : 3;
+        nc_total *= (double)g.nc[d];
+    }
+    if (nc_total > 2147483000.0) {
+        set_error("cell grid too large: " + std::to_string(nc_total) + " cells (the reference indexes cells with int32)");
+        return MDH_ERR_ARG;
+    }
+    g.ncell = (int64_t)g.nc[0] * g.nc[1] * g.nc[2];
+    g.rc_inv = 1.0 / rc; // neighbor.cpp:78
+    g.mode = 0;
+    return MDH_OK;
+}
+
+// Do the atoms come in a spatial order?  One workgroup samples 1 024 pairs of consecutive atoms (i, i+1): far = more than two
+// bins of ~64 atoms apart along some axis (fractional coordinates, periodic axes wrapped); more than a quarter far -> *flag = 1 (a word
+// of pinned host memory, order_hint()): the NEXT builds of this (N, grid) move whole 32-byte records (k_assign writes them in input
+// order, the gather reads one random sector per atom instead of three or four: 598 -> ~250 us at 10 M shuffled atoms).  A lattice
+// builder's order, a file written cell by cell, a sorted copy: 0.  Launched on the first and every eighth build of a signature.
+__global__ __launch_bounds__(1024) void k_order_far_flag(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+                                                         int64_t N, DBox b, double nb0, double nb1, double nb2, int *__restrict__ flag)
+{
+    __shared__ int s_far;
+    if (threadIdx.x == 0) s_far = 0;
+    __syncthreads();
+    const int64_t step = (N - 1) / 1024 > 0 ? (N - 1) / 1024 : 1;
+    const int64_t i = (int64_t)threadIdx.x * step;
+    bool far = false;
+    if (i + 1 < N) {
+        const double dx = x[i + 1] - x[i], dy = y[i + 1] - y[i], dz = z[i + 1] - z[i];
+        double f[3] = {dx * b.hi[0] + dy * b.hi[3] + dz * b.hi[6], dx * b.hi[1] + dy * b.hi[4] + dz * b.hi[7], dx * b.hi[2] + dy * b.hi[5] + dz * b.hi[8]};
+        const double nb[3] = {nb0, nb1, nb2};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            if (b.pbc[d]) f[d] -= rint(f[d]);
+            far = far || !(fabs(f[d]) * nb[d] <= 2.0); // (NaN counts as far)
+        }
+    }
+    const unsigned long long m = __ballot(far);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_far, __popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0) *flag = 4 * s_far > 1024 ? 1 : 0;
+}
+
+int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b, const GridRequest &rq,
+                    CellGrid &cg)
+{
+    PendingWindows hints; // (from here on values: only a build for neighbor rows uses them, below)
+    MDH_TRY(take_pending_windows(hints));
+    const CellWindow &window = hints.cells, &centre = hints.centre;
+    const bool packed = rq.atoms != GridRequest::SORTED_ARRAYS;
+    bool scattered = rq.atoms == GridRequest::FOR_ROWS_UNORDERED;
+    const Grid &g = cg.g;
+    hipStream_t st = sc.stream();
+
+    // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
+    // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
+    unsigned *cell_count = static_cast<unsigned *>(sc.alloc_kept(sizeof(unsigned) * (size_t)g.ncell, Scope::KEEP_ZERO));
+    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
+    cg.flags = sc.alloc_n<int>(8);
+    cg.cell_start = sc.alloc_n<int>((size_t)g.ncell + 1);
+    int2 *ent = sc.alloc_n<int2>((size_t)N); // (cell, slot) of every atom: k_assign -> k_scatter
+    int *rank = reinterpret_cast<int *>(ent); // ... and, once the atoms are scattered, the N ints of scratch of the in-cell sorts
+    cg.order = sc.alloc_n<int>((size_t)N + 4); // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
+    unsigned short *mv = sc.alloc_n<unsigned short>((size_t)N);
+    cg.xs = cg.ys = cg.zs = nullptr;
+    cg.mvs = nullptr;
+    cg.pk = nullptr;
+    // scattered (FOR_ROWS_UNORDERED): the caller knows that the atoms come in no spatial order
+    CellGrid::Packed *rec = nullptr;
+    int *rec_flag = nullptr;
+    cg.ix = cg.iy = cg.iz = nullptr;
+    cg.imv = nullptr;
+    if (packed) {
+        // records: always for a caller that knows (scattered); for a large system otherwise when the last sample of this (N, grid) said so
+        if (!scattered && N >= (int64_t(1) << 18)) {
+            const OrderHint h = order_hint(1, N, g.ncell, x);
+            scattered = h.word && *(volatile int *)h.word != 0;
+            if (h.word && h.sample) rec_flag = h.word;
+        }
+        // input in some spatial order: no sorted copy, the kernels read through `order` (CellGrid::ix); MDH_INDIRECT=0 /
+        // mdh_debug_set_indirect(0): the records always — an A/B switch, and how the tests reach both paths on one input
+        // (not for dense cells — six atoms and more, the wide instance's ground: two workgroups per CU hide the staging's
+        // dependent gathers badly, build_neighbor(5.0, 50) at 10 M atoms 4.48 -> 4.60 ms; profiles/r06_cell_grid_ab.txt)
+        const bool indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && rq.sort_desc && (double)N <= 6.0 * (double)g.ncell && rq.row_width <= 16;
+        if (!indirect) cg.pk = sc.alloc_n<CellGrid::Packed>((size_t)N);
+        if (scattered) rec = sc.alloc_n<CellGrid::Packed>((size_t)N);
+    } else {
+        cg.xs = sc.alloc_n<double>((size_t)N);
+        cg.ys = sc.alloc_n<double>((size_t)N);
+        cg.zs = sc.alloc_n<double>((size_t)N);
+        cg.mvs = sc.alloc_n<unsigned short>((size_t)N);
+    }
+    if (sc.failed())
+        return sc.error();
+
+    // window of planes along axis 0 (orthogonal boxes, rc-wide cells): [p0, p1) and, when it wraps around the ring, [p2, p3)
+    int p0 = 0, p1 = g.nc[0], p2 = 0, p3 = 0;
+    bool windowed = false;
+    if (window.set) {
+        const CellWindow &w = window;
+        // (only the neighbor builds — the callers of the packed record — know what a window leaves undone; a hint that meets
+        // any other grid build is dropped)
+        if (packed && w.axis == 0 && !b.tri && g.mode == 0 && g.nc[0] >= 16 && w.hi > w.lo && w.hi - w.lo < 0.75) {
+            const double L = b.h[0];
+            int lo = (int)std::floor(w.lo * L * g.rc_inv) - 1, hi = (int)std::ceil(w.hi * L * g.rc_inv) + 1; // one plane of margin
+            if (hi - lo < g.nc[0] - 2) {
+                windowed = true;
+                if (lo < 0) { p0 = 0; p1 = std::min(hi, g.nc[0]); p2 = g.nc[0] + lo; p3 = g.nc[0]; }         // wraps below
+                else if (hi > g.nc[0]) { p0 = 0; p1 = hi - g.nc[0]; p2 = lo; p3 = g.nc[0]; }                   // wraps above
+                else { p0 = lo; p1 = hi; p2 = p3 = 0; }
+                if (p2 < p1 && p3 > p2) { windowed = false; p0 = 0; p1 = g.nc[0]; p2 = p3 = 0; }               // (the pieces meet: everything)
+            }
+        }
+    }
+    const int64_t plane = (int64_t)g.nc[1] * g.nc[2];
+    cg.win_lo = cg.win_hi = 0;
+    if (windowed && p3 <= p2) { cg.win_lo = p0; cg.win_hi = p1; } // one piece: the tile kernel runs over its range of tiles
+    cg.cen_lo = cg.cen_hi = 0;
+    if (centre.set) {
+        const CellWindow &c = centre;
+        if (packed && c.axis == 0 && !b.tri && g.mode == 0 && c.hi > c.lo && c.lo >= 0.0 && c.hi <= 1.0) {
+            // the planes an atom of fraction [lo, hi) can be binned into (cell_coords: floor((x - o) rc_inv), clamped); the ends moved
+            // out by 1e-9 of their value — far more than the roundings that separate the caller's fraction of an atom from the grid's
+            // (x - o) rc_inv, far less than a plane: an atom ON the slab's face is inside whichever way it was rounded
+            const double L = b.h[0];
+            cg.cen_lo = std::max(0, std::min(g.nc[0] - 1, (int)std::floor(c.lo * L * g.rc_inv * (1.0 - 1e-9) - 1e-9)));
+            cg.cen_hi = std::min(g.nc[0], (int)std::floor(c.hi * L * g.rc_inv * (1.0 + 1e-9) + 1e-9) + 1);
+        }
+    }
+    cg.flags_fresh = true;
+    // slack for the raw-vs-wrapped consistency flag: far above rounding, far below a cell width
+    const double slack = 0.01 / (g.rc_inv > 0 ? g.rc_inv : 1.0);
+    // the promise is checked where the atoms are binned (a word of pinned host memory the kernel writes) and read by the next
+    // build of this thread or by mdh_cell_window_check
+    CellPlanes win{p0, p1, p2, p3, nullptr};
+    if (windowed) {
+        if (!g_window_violations) MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&g_window_violations), sizeof(int), hipHostMallocDefault));
+        *g_window_violations = 0;
+        win.bad = g_window_violations;
+    }
+    if (rec_flag) {
+        const double *h = b.h;
+        const double vol = std::fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]));
+        const double edge = std::cbrt(64.0 * vol / (double)N);
+        double nb[3];
+        for (int d = 0; d < 3; ++d) nb[d] = std::max(1.0, std::floor(b.thick[d] / edge));
+        hipLaunchKernelGGL(k_order_far_flag, dim3(1), dim3(1024), 0, st, x, y, z, N, b, nb[0], nb[1], nb[2], rec_flag);
+    }
+    const unsigned gen = next_scan_gen(); // stamps of this build's k_assign; the (first) scan below is launched with the same value
+    // atoms per lane: four; small systems keep one atom per lane (they need the workgroups to fill the chip)
+    // (measured at 10 M atoms, with the grouping of round 5 — runs of adjacent lanes: 145 -> 120 us on a lattice, 162 -> 162 on a polycrystal — 10 M runs of one atom, the atomics' own
+    // throughput — 413 -> 440 on a shuffled frame, which therefore keeps one: profiles/r05_assign_k.txt)
+    const bool assign4 = N >= (int64_t)1 << 20 && !scattered;
+#define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)rq.wrap_first, ent, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
+    if (b.tri) {
+        if (assign4) MDH_ASSIGN(true, 4); else MDH_ASSIGN(true, 1);
+    } else {
+        if (assign4) MDH_ASSIGN(false, 4); else MDH_ASSIGN(false, 1);
+    }
+#undef MDH_ASSIGN
+    auto scan_piece = [&](int64_t from, int64_t to, unsigned use_gen, int *flags) {
+        launch_scan_gen(st, cell_count + from, cg.cell_start + from, to - from, ctl, use_gen, true, flags); // [to] = the piece's total
+    };
+    if (!windowed) {
+        scan_piece(0, g.ncell, gen, cg.flags);
+    } else {
+        // the pieces in index order: [p0, p1) then [p2, p3); a piece is scanned on its own, the atoms before it added by the
+        // fill / by a second add pass; cell_start elsewhere = what a full scan leaves: the atoms binned so far.  The counters
+        // outside the window are zero (kept block; atoms out there take no slot) and stay untouched.
+        const int64_t a0 = p0 * plane, a1 = p1 * plane, b0 = p2 * plane, b1 = p3 * plane;
+        // (constant fills through the runtime's fill kernel: 16-byte stores, 5 us per 10 MB against 15 of a store per thread)
+        hipError_t fill_err = hipSuccess;
+        auto fill_const = [&](int64_t from, int64_t to, int v) {
+            if (to > from && fill_err == hipSuccess)
+                fill_err = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cg.cell_start + from), v, (size_t)(to - from), st);
+        };
+        if (b1 > b0) fill_const(0, a0, 0);
+        // (from a multiple of four cells on: the scan moves 16 bytes per access only from an aligned start — 66 against 26 us for the
+        // 3.6 M cells of a 10 M-atom slab; the up to three counters in front of the window are zero, and zero is what the cells in
+        // front of the window hold)
+        scan_piece(a0 & ~(int64_t)3, a1, gen, cg.flags);
+        if (b1 <= b0) { // one piece: everything outside it in one launch
+            const int64_t n1 = g.ncell + 1, quads = ((a0 + 3) >> 2) + ((n1 - std::min(n1, (a1 + 1 + 3) & ~(int64_t)3) + 3) >> 2) + 1;
+            hipLaunchKernelGGL(k_fill_outside, dim3(grid_for(quads, 256)), dim3(256), 0, st, cg.cell_start, a0, a1, n1, cg.cell_start + a1);
+        } else if (b1 > b0) {
+            // second piece: offsets start at the first piece's total, which sits on the device in cell_start[a1]
+            fill_from(st, cg.cell_start, a1 + 1, b0, cg.cell_start + a1);
+            scan_piece(b0, b1, next_scan_gen(), nullptr);
+            hipLaunchKernelGGL(k_add_from, dim3(grid_for(b1 - b0 + 1, 256)), dim3(256), 0, st, cg.cell_start, b0, b1 + 1, cg.cell_start + a1, (int64_t)-1);
+            // behind the window: the number of atoms BINNED (cell_start[b1], on the device) — N unless the promise was broken; with
+            // the constant N a cell behind a broken window spanned the records [n_binned, N), which k_scatter / k_gather never wrote
+            if (b1 < g.ncell)
+                fill_from(st, cg.cell_start, b1 + 1, g.ncell + 1, cg.cell_start + b1);
+        }
+        MDH_HIP(fill_err);
+    }
+    sc.keep_confirm(cell_count); // every counter a binned atom touched has been read and cleared by a scan enqueued above
+    hipLaunchKernelGGL(k_scatter, dim3(grid_for((N + 1) / 2, 256)), dim3(256), 0, st, ent, cg.cell_start, cg.order, N);
+    if (rq.sort_desc) {
+        if (!windowed && !rq.sort_key && (double)N > 6.0 * (double)g.ncell) {
+            hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rank);
+        } else if (!windowed) {
+            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rq.sort_key, rank);
+        } else {
+            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p1 - p0) * plane, 256)), dim3(256), 0, st, cg.cell_start + p0 * plane, cg.order, (p1 - p0) * plane, rq.sort_key, rank);
+            if (p3 > p2)
+                hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p3 - p2) * plane, 256)), dim3(256), 0, st, cg.cell_start + p2 * plane, cg.order, (p3 - p2) * plane, rq.sort_key, rank);
+        }
+    }
+    // (the atoms binned = the grid's total, on the device: all N unless absent atoms were handed in or a window's promise was broken)
+    const int *n_binned = cg.cell_start + g.ncell;
+    if (packed && !cg.pk) { cg.ix = x; cg.iy = y; cg.iz = z; cg.imv = mv; } // indirect: nothing is gathered
+    else if (rec) hipLaunchKernelGGL(k_gather_records, dim3(grid_for(N, 256)), dim3(256), 0, st, rec, cg.order, cg.pk, N, n_binned);
+    else hipLaunchKernelGGL(k_gather, dim3(grid_for(N, 256)), dim3(256), 0, st, x, y, z, cg.order, cg.xs, cg.ys, cg.zs, N, mv, cg.mvs, cg.pk, cg.flags + 4, n_binned);
+    MDH_HIP(hipGetLastError());
+    return MDH_OK;
+}
+
+} // namespace mdh
+
+using namespace mdh;
+
+extern "C" {
+
+int mdh_hint_centre_window(int axis, double frac_lo, double frac_hi)
+{
+    g_pending.centre = CellWindow{axis, frac_lo, frac_hi, true};
+    return MDH_OK;
+}
+
+int mdh_hint_cell_window(int axis, double frac_lo, double frac_hi)
+{
+    g_pending.cells = CellWindow{axis, frac_lo, frac_hi, true};
+    return MDH_OK;
+}
+
+int mdh_cell_window_check(void *stream)
+{
+    if (!g_window_violations)
+        return MDH_OK;
+    MDH_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    if (*(volatile int *)g_window_violations != 0) {
+        *g_window_violations = 0;
+        set_error("the last neighbor build on this thread found atoms outside the cell window it had been promised (mdh_hint_cell_window): its rows are incomplete");
+        return MDH_ERR_ARG;
+    }
+    return MDH_OK;
+}
+
+int mdh_debug_set_indirect(int on) { return g_indirect.exchange(on ? 1 : 0); }
+}
+
+MDH_WARM_UNIT(cell_grid)
+
+// the grouping rule of k_assign on the host (assign_groups.hpp), slice by slice
+extern "C" int64_t mdh_debug_assign_groups(const int *cells, int64_t n, int *head, int *count, int *rank)
+{
+    int64_t atomics = 0;
+    for (int64_t s0 = 0; s0 < n; s0 += 64) {
+        int c[64], h[64], k[64], r[64];
+        for (int l = 0; l < 64; ++l) c[l] = s0 + l < n ? cells[s0 + l] : -1 - l;
+        mdh::assign_groups::slice(c, h, k, r);
+        for (int l = 0; l < 64 && s0 + l < n; ++l) {
+            head[s0 + l] = h[l]; count[s0 + l] = k[l]; rank[s0 + l] = r[l];
+            atomics += k[l] > 0 && c[l] >= 0 ? 1 : 0;
+        }
+    }
+    return atomics;
+}

@@ -33,10 +33,10 @@ __host__ __device__ __forceinline__ int combine(int cc, int ca)
 __host__ __device__ __forceinline__ int axis(int code, int d) { return ((code >> (5 * d)) & 31) - 16; } // image number of a combined code
 } // namespace img
 
-// device buffers produced by build_cell_grid (owned by the Scope that built them)
+// device buffers produced by build_cell_grid, cell_grid.hip (owned by the Scope that built them)
 struct CellGrid {
     Grid g;
-    int win_lo = 0, win_hi = 0; // planes [win_lo, win_hi) of axis 0 the grid was built over (a promised window, neighbor.hip); 0, 0: all
+    int win_lo = 0, win_hi = 0; // planes [win_lo, win_hi) of axis 0 the grid was built over (a promised window, cell_grid.hip); 0, 0: all
     int cen_lo = 0, cen_hi = 0; // planes [cen_lo, cen_hi) of axis 0 whose atoms want rows (mdh_hint_centre_window: a slab's own atoms; the rest of the window is halo); 0, 0: all
     mutable bool flags_fresh = false; // flags[] were zeroed by build_cell_grid and nobody has used them yet (the first neighbor pass skips its own memset: every hipMemsetAsync is a 5 us launch)
     int *cell_start; // [ncell+1] exclusive prefix of the per-cell populations
@@ -104,8 +104,28 @@ struct TileFilter {
 // occupied_cells: cells that hold atoms (occupied_cells_hint); 0 = assume all of them
 TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells);
 int occupied_cells_hint(Scope &sc, const CellGrid &cg, int64_t N, int64_t *occupied);
+
+// What one pass over a built cell grid is to leave behind (neighbor.hip neighbor_pass and the kernels' launchers)
+struct RowsRequest {
+    // COUNT_ONLY: nn and *max_count only (first pass of the exact-width variant): no rows, M is 1
+    // KEEP_PADS:  reference semantics: valid slots written, the slots behind them keep what the caller put there
+    // WRITE_PADS: ... and the slots behind them written too (-1, rc + 1)
+    enum Pads { COUNT_ONLY, KEEP_PADS, WRITE_PADS };
+    int *verlet = nullptr;  // [N][M] rows in original atom order
+    double *dist = nullptr; // [N][M]
+    int *nn = nullptr;      // [N] counts (they keep running past M)
+    int64_t M = 1;
+    Pads pads = WRITE_PADS;
+    // nobody reads the distances (knn.hip: rows as candidates of a k-nearest search; 8 M bytes per atom written and ~300 instructions
+    // per four slots saved): the tile kernel's wide instance writes ids and counts only, every other kernel distances as always
+    bool ids_only = false;
+    int *max_count = nullptr; // COUNT_ONLY: the largest count (device word, zeroed by the caller)
+    // pattern != nullptr (not COUNT_ONLY): the fixed-cutoff CNA label (cna.cpp:429-506, same rc) of every centre the tile kernel
+    // takes is written too; the atoms its mop-up kernels take are listed in todo (count first) for a pass over the finished rows
+    int *pattern = nullptr, *todo = nullptr;
+};
 int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, int64_t N, const DBox &b, double rc,
-                          int *verlet, double *dist, int *nn, int64_t M, bool fill_pads, TileFilter &tf);
+                          const RowsRequest &rows, TileFilter &tf);
 
 // neighbor_lane.hip: LDS tiles, one thread per centre atom, single-precision pruning (see the file header)
 struct GridStats {
@@ -128,10 +148,12 @@ struct LanePlan {
 int grid_stats_hint(Scope &sc, const CellGrid &cg, int64_t N, GridStats *out);
 LanePlan plan_lane(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count);
 int lane_last_listed(); // tiles listed for the slice pass as last seen when a plan was made (mdh_debug_counters)
-// pattern != nullptr: the fixed-cutoff CNA label (cna.cpp:429-506, same rc) of every centre the kernel takes is written too
 int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, int64_t N, const DBox &b, double rc,
-                         int *verlet, double *dist, int *nn, int64_t M, bool fill_pads, bool count, int *max_count,
-                         TileFilter &tf, int *pattern = nullptr);
+                         const RowsRequest &rows, TileFilter &tf);
+// neighbor.hip, for other units of the library (knn.hip): the rows of a cutoff build on device arrays — its own cell grid, pads
+// written (-1 / rc + 1), counts that keep running past M — enqueued on the Scope's stream.  ids_only: RowsRequest::ids_only
+int neighbor_rows_device(Scope &sc, const double *dx, const double *dy, const double *dz, int64_t N, const DBox &b, double rc, int *dv,
+                         double *dd, int *dn, int64_t M, const int64_t *dkey, bool ids_only);
 // cna.hip: fixed-cutoff CNA from finished lists on the caller's stream — of all atoms, or of the atoms listed in todo
 // (todo[0] = count, device side) with the reference expression
 // done != nullptr: todo sits in a kept block (Scope::KEEP_TODO) — the kernel that walks the list clears its counters when it leaves
@@ -188,15 +210,27 @@ __device__ __forceinline__ void cell_coords(const DBox &b, const Grid &g, double
 // fills cg.g for the cutoff neighbor search: nc = max(floor(thickness/rc), 3) (neighbor.cpp:203-206)
 int neighbor_grid_dims(const DBox &b, double rc, Grid &g);
 
-// Bins the atoms into cg.g (dims/mode set by the caller) and produces cell_start/order/xs,ys,zs.
-//   wrap_first : wrap a position into the primary cell before binning when any axis is periodic
-//   sort_desc  : order every cell's atoms by descending id (reference row order); otherwise the
-//                order inside a cell is whatever the atomic counters produced
-int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b,
-                    bool wrap_first, bool sort_desc, CellGrid &cg, const int64_t *sort_key = nullptr, bool packed = false,
-                    bool scattered = false);
+// What build_cell_grid is asked for
+struct GridRequest {
+    // SORTED_ARRAYS:      xs, ys, zs, mvs: the atoms as coordinate arrays in cell order (kNN, RDF, Voronoi, the overlap filter)
+    // FOR_ROWS:           for neighbor rows: the 32-byte records (CellGrid::pk), or no sorted copy at all (CellGrid::ix)
+    // FOR_ROWS_UNORDERED: ... of input the caller knows to come in no spatial order (mdh_spatial_sort): records, moved whole
+    enum Atoms { SORTED_ARRAYS, FOR_ROWS, FOR_ROWS_UNORDERED };
+    bool wrap_first = false; // wrap a position into the primary cell before binning when any axis is periodic
+    bool sort_desc = false;  // every cell's atoms by descending id (reference row order); else as the atomic counters placed them
+    const int64_t *sort_key = nullptr; // [N] descending key[id] instead of descending id
+    Atoms atoms = SORTED_ARRAYS;
+    // FOR_ROWS: width of the rows about to be built (0: not known, or counting).  Rows of more than 16 slots go to the tile kernel's
+    // wide instance, which hides the indirect staging's gathers badly (two or three workgroups per CU): such a build keeps the
+    // records (the 12-nearest search's cutoff build, 4.7 atoms per cell, rows of 24: 2.15 ms with records, 2.22 without)
+    int row_width = 0;
+};
+// Bins the atoms into cg.g (dims/mode set by the caller) and produces cell_start/order and the atoms as rq.atoms says; takes the
+// thread's pending window hints (mdh_hint_cell_window, mdh_hint_centre_window), whatever the build is for
+int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b, const GridRequest &rq,
+                    CellGrid &cg);
 
-// neighbor.hip: out[0..n] = exclusive prefix sums of in[0..n), out[n] = total
+// cell_grid.hip: out[0..n] = exclusive prefix sums of in[0..n), out[n] = total
 int exclusive_scan_u32(Scope &sc, const unsigned *in, int *out, int64_t n);
 
 } // namespace mdh

@@ -26,9 +26,6 @@
 
 namespace mdh {
 
-int neighbor_rows_device(Scope &sc, const double *dx, const double *dy, const double *dz, int64_t N, const DBox &b, double rc, int *dv,
-                         double *dd, int *dn, int64_t M, const int64_t *dkey, bool ids_only); // neighbor.hip
-
 int g_knn_variant = 0; // 0 = near kernel + general kernel, 1 = general kernel only (tests, A/B), 3 = counting kernel first (measuring variant)
 
 struct KnnGeom {
@@ -790,7 +787,7 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
                 // an atom the build does not bin (a NaN coordinate) gets no row and no count: 0, so that k_knn_rows flags it for the
                 // cell walk instead of reading a row nobody wrote
                 MDH_HIP(hipMemsetAsync(rnn, 0, (size_t)N * sizeof(int), st));
-                MDH_TRY(neighbor_rows_device(sc, dx, dy, dz, N, b, r, rows, rdist, rnn, M, nullptr, true));
+                MDH_TRY(neighbor_rows_device(sc, dx, dy, dz, N, b, r, rows, rdist, rnn, M, nullptr, /*ids_only=*/true));
             }
             if (kept && radius) *radius = r;
             ProfRange pr("knn_rows_select", st);
@@ -881,7 +878,7 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
     cg.g.ncell = (int64_t)cg.g.nc[0] * cg.g.nc[1] * cg.g.nc[2];
     cg.g.rc_inv = 0.0;
     cg.g.mode = 1;
-    MDH_TRY(build_cell_grid(sc, wx, wy, wz, N, bg, false, false, cg));
+    MDH_TRY(build_cell_grid(sc, wx, wy, wz, N, bg, GridRequest{}, cg)); // (positions wrapped above; sorted coordinate arrays, cells in any order)
     int *label = nullptr, *unlabel = nullptr;
     if (key) {
         label = sc.alloc_n<int>((size_t)N);

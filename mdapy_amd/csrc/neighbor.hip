@@ -1,867 +1,21 @@
-// neighbor.hip — cell-list cutoff neighbor search on gfx950.
+// neighbor.hip — cell-list cutoff neighbor search on gfx950: the thread-per-atom kernels, the pass over a built cell grid
+// (cell_grid.hip) that chooses among them and the tile kernels (neighbor_lane.hip, neighbor_tiled.hip), the row utilities and
+// the C entry points.  Replaces src/neighbor.cpp of the reference (build_verlet_list :102-187, build_neighbor :351-388, the
+// exact-width variant :189-349, sort_verlet_by_distance :745-775, wrap_positions :675-702, average_by_neighbor :704-743).
 //
-// Replaces src/neighbor.cpp of the reference (build_cell :64-100,
-// build_verlet_list :102-187, build_neighbor :351-388, the exact-width variant
-// :189-349, sort_verlet_by_distance :745-775, wrap_positions :675-702,
-// average_by_neighbor :704-743).
-//
-// Data layout in HBM:
-//   caller:  x,y,z f64[N] (SoA, original atom order); verlet int32[N][M],
-//            dist f64[N][M], nn int32[N]   — rows in ORIGINAL atom order.
-//   scratch: cell_count u32[ncell] -> cell_start i32[ncell+1] (exclusive scan),
-//            ent int2[N] ((cell, slot handed out by the cell's atomic counter) of every atom: k_assign -> k_scatter; afterwards
-//                           N ints of scratch for the in-cell sorts),
-//            order i32[N]  (atom ids sorted by cell; inside a cell DESCENDING id,
-//                           the order in which the reference's head-inserted
-//                           linked list is walked),
-//            xs,ys,zs f64[N] (raw positions gathered into cell order, so a
-//                           cell's atoms — and the 3 cells of a z-run — are
-//                           contiguous and loads are coalesced).
+// Data layout in HBM: x,y,z f64[N] (SoA, original atom order); verlet int32[N][M], dist f64[N][M], nn int32[N] —
+// rows in ORIGINAL atom order; scratch: the cell grid (CellGrid in grid.hpp).
 #include "common.hpp"
 #include "grid.hpp"
 #include "cna_core.hpp"
-#include "assign_groups.hpp"
 #include <algorithm>
-#include <atomic>
 #include <mutex>
 #include <vector>
 
 namespace mdh {
 
 static int *g_moved_probe = nullptr; // pinned: flags[0] of the last tracked neighbor pass (mdh_debug_track_counters)
-// 1: neighbor builds of input in spatial order keep no sorted copy of the atoms (CellGrid::ix); 0: the 32-byte records always
-static std::atomic<int> g_indirect{[] { const char *e = std::getenv("MDH_INDIRECT"); return e ? std::atoi(e) : 1; }()};
-// Row width of the build the NEXT packed cell grid of this thread is for (0: not known).  Rows of more than 16 slots go to the tile
-// kernel's wide instance, which hides the indirect staging's gathers badly (two or three workgroups per CU): such a build keeps
-// the records (the 12-nearest search's cutoff build, 4.7 atoms per cell, rows of 24: 2.15 ms with records, 2.22 without)
-static thread_local int g_next_rows = 0;
-int g_neighbor_variant = 0; // 0 = automatic, 1 = force the thread-per-atom kernel, 2 = force the round-1 LDS-tiled kernel (A/B measurements, tests)
-
-// ----------------------------------------------------------------------------
-// cell assignment: wrap, bin, take a slot from the cell's atomic counter
-// ----------------------------------------------------------------------------
-struct CellPlanes { int p0, p1, p2, p3; int *bad; }; // planes [p0, p1) and [p2, p3) of axis 0 hold every atom (bad == nullptr: not promised; else a pinned host word)
-// K atoms per lane: a wave takes 64 * K consecutive atoms as K slices of 64 (slice k: atom base + 64 k + lane, so adjacent lanes
-// still hold adjacent atoms and the groups below are found per slice).  The kernel is a chain of dependent memory trips — position
-// loads, the returning atomic, the store — at full occupancy (26-38 VGPRs; 87 % of the wave-cycles waiting,
-// profiles/r05_step_counters.json): with K > 1 the loads of a lane's K atoms are in flight together, and so are its K atomics.
-// One atomic per group of lanes of a cell up to three lanes apart (assign_groups.hpp) and ONE 8-byte store of (cell, slot) per atom:
-// 133.8 -> 90-104 us at 10 M lattice atoms (8.23 M -> 6.73 M atomics, the distinct cells per slice; with runs of adjacent lanes and
-// two 4-byte stores before), profiles/assign_window.md.
-template <bool TRI, int K>
-__global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, const double *__restrict__ y,
-                                                const double *__restrict__ z, int64_t N, DBox b, Grid g,
-                                                int wrap_first, int2 *__restrict__ ent,
-                                                unsigned *__restrict__ cell_count, unsigned *__restrict__ ctl, unsigned gen,
-                                                double slack, unsigned short *__restrict__ mv, CellPlanes win,
-                                                CellGrid::Packed *__restrict__ rec, int drop_absent)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t i0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * (64 * K) + lane;
-    bool moved = false, outside = false, coded = false;
-    double xr[K], yr[K], zr[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) { // (all loads of the lane first)
-        const int64_t i = i0 + 64 * k;
-        xr[k] = yr[k] = zr[k] = 0.0;
-        if (i < N) { xr[k] = x[i]; yr[k] = y[i]; zr[k] = z[i]; }
-    }
-    int cells[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int64_t i = i0 + 64 * k;
-        int cell = -1 - lane; // lanes past the end, absent atoms: negative, no group, no atomic
-        // an atom whose x is NaN is ABSENT: it takes no cell, appears in nobody's row and gets no row of its own (the unused slots of a
-        // decomposed system's fixed-size ghost block, slab.hip k_slab_append_static; the reference has no meaning for such input)
-        // (only the neighbor builds — drop_absent — know what to do without such an atom: their kernels walk cells, and their per-atom
-        // passes end at the number of atoms binned; every other user of the grid bins a NaN as it always did, into cell 0)
-        const bool absent = drop_absent && i < N && xr[k] != xr[k];
-        if (absent && mv) mv[i] = (unsigned short)img::ATOM_NEUTRAL;
-        if (i < N && !absent) {
-            double xi = xr[k], yi = yr[k], zi = zr[k];
-            int code = img::ATOM_NEUTRAL; // (m + 15) per axis: raw = wrapped + m*L
-            if (wrap_first && b.anypbc) { // neighbor.cpp:88-91
-                wrap<TRI>(b, xi, yi, zi);
-                if (!TRI) {
-                    // whole box lengths between the raw and the wrapped coordinate (an unwrapped trajectory: a few); more than
-                    // img::MAX_M of them, or a coordinate that is not wrapped + m L to within `slack`, invalidates the image codes
-                    // for this call (flags[0])
-                    const double raw[3] = {xr[k], yr[k], zr[k]}, wrp[3] = {xi, yi, zi};
-                    code = 0;
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        double m = 0.0;
-                        if (b.pbc[d] && raw[d] != wrp[d]) { // already wrapped (the common case): m = 0, no division
-                            m = rint((raw[d] - wrp[d]) / b.h[d * 4]);
-                            if (!(fabs(m) <= (double)img::MAX_M) || !(fabs(raw[d] - m * b.h[d * 4] - wrp[d]) <= slack)) { moved = true; m = 0.0; }
-                        }
-                        code |= ((int)m + 15) << (5 * d);
-                    }
-                }
-            }
-            if (mv) mv[i] = (unsigned short)code;
-            // scattered input (mdh_spatial_sort): the atom as ONE 32-byte record in input order — the gather then reads one random
-            // sector per atom instead of three (x, y, z) or four (the image code)
-            if (rec) rec[i] = CellGrid::Packed{xr[k], yr[k], zr[k], (int)i, code};
-            coded = coded || code != img::ATOM_NEUTRAL;
-            int c0, c1, c2;
-            cell_coords<TRI>(b, g, xi, yi, zi, c0, c1, c2);
-            cell = (c0 * g.nc[1] + c1) * g.nc[2] + c2; // neighbor.cpp:24-27 (ncell < 2^31 checked on the host)
-            if (win.bad && !((c0 >= win.p0 && c0 < win.p1) || (c0 >= win.p2 && c0 < win.p3))) {
-                // an atom outside the window of planes the caller promised (mdh_hint_cell_window): the counters out there were
-                // never zeroed — it takes no slot and is not scattered (cell -1); the build is reported broken (win.bad), its
-                // rows are not to be used, and nothing is written out of bounds
-                outside = true;
-                cell = -1 - lane;
-            }
-        }
-        cells[k] = cell;
-    }
-    // One returning atomic per GROUP of lanes in the same cell instead of one per atom: atoms usually arrive in some spatial
-    // order (a lattice builder, a file written cell by cell, a previous sort), so nearby lanes share cells; the slot inside a
-    // cell is arbitrary anyway (k_sort_cells restores the reference's order).  A group is a head and the lanes of its cell up
-    // to three behind it (assign_groups.hpp: the basis atoms of an fcc cell alternate between grid cells, A B A B), or, where
-    // that makes fewer atomics of the slice, a run of adjacent lanes.  Unordered input pays four shuffles (three up, one from the
-    // head) and seven ballots (primary heads, run starts, the two counts of atomics, the members at distance 1, 2, 3).
-    unsigned base[K];
-    int head[K], slot[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) { // (the K atomics of the lane in flight together)
-        const int cell = cells[k];
-        const int c1 = __shfl_up(cell, 1, 64);
-        const unsigned eq = assign_groups::equal_bits(cell, c1, __shfl_up(cell, 2, 64), __shfl_up(cell, 3, 64), lane);
-        const unsigned long long primary = __ballot(eq == 0);
-        int d = assign_groups::member_distance(eq, primary, lane);
-        const bool start = assign_groups::starts_run(cell, c1, lane);
-        const unsigned long long starts = __ballot(start);
-        int count;
-        if (assign_groups::use_runs(__popcll(__ballot(start && cell >= 0)), __popcll(__ballot(d == 0 && cell >= 0)))) // (wave-uniform)
-            d = assign_groups::run_distance(starts, lane, &count, &slot[k]);
-        else
-            assign_groups::count_and_rank(d, __ballot(d == 1), __ballot(d == 2), __ballot(d == 3), lane, &count, &slot[k]);
-        head[k] = lane - d;
-        base[k] = 0;
-        if (d == 0 && cell >= 0)
-            base[k] = atomicAdd(&cell_count[cell], (unsigned)count);
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const unsigned bs = __shfl(base[k], head[k], 64);
-        const int64_t i = i0 + 64 * k;
-        if (i < N) // (cell < 0: absent, or outside a promised window — k_scatter leaves the atom out)
-            ent[i] = make_int2(cells[k], (int)(bs + (unsigned)slot[k]));
-    }
-    // what this kernel finds out about the input goes into generation-stamped control words (no memset per build): the scan
-    // that follows turns them into the build's flags[0] (unwrapped input) and flags[4] (image codes present)
-    if (__any(moved) && lane == 0)
-        ctl[1] = gen;
-    if (__any(coded) && lane == 0)
-        ctl[2] = gen; // some atom was handed in outside the box: the gather has to read the image codes (else they are all neutral)
-    if (__any(outside) && lane == 0)
-        *win.bad = 1; // (pinned host memory: read by the next build of the thread / mdh_cell_window_check)
-}
-
-// ----------------------------------------------------------------------------
-// exclusive prefix sum of the bin counters (three small kernels)
-// ----------------------------------------------------------------------------
-static constexpr int SCAN_BLOCK = 256;
-static constexpr int SCAN_ITEMS = 4; // per thread -> 1024 per block (small inputs); SCAN_ITEMS_BIG for large ones
-static constexpr int SCAN_ITEMS_BIG = 32; // 8192 per block: every block takes a ticket from ONE word, ~90 of them per microsecond —
-                                          // with 1024 per block the 3 925 tickets of a 4 M-cell grid were 43 of the scan's 62 us
-static constexpr int64_t SCAN_BIG_FROM = 1 << 19; // items from which the big blocks are used
-
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        unsigned t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one value per thread (256 threads = 4 waves); returns exclusive prefix, total via *tot
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *tot)
-{
-    __shared__ unsigned wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned inc = wave_incl_scan(v, lane);
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    unsigned off = 0, t = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < w) off += wsum[k];
-        t += wsum[k];
-    }
-    __syncthreads();
-    *tot = t;
-    return off + inc - v;
-}
-
-// ----------------------------------------------------------------------------
-// Single-pass exclusive scan (decoupled look-back: Merrill & Garland, "Single-pass parallel prefix scan with decoupled
-// look-back", NVIDIA NVR-2016-002) — ONE launch instead of three: at a few thousand atoms a build is a chain of dependent
-// launches of ~4 us each, whatever they do.  A block takes a ticket (so that every predecessor it waits for is already
-// running), scans its 1024 items, publishes its total, and wave 0 collects the totals / inclusive prefixes of the blocks
-// before it, 64 at a time.  Control words live in a kept block (Scope::KEEP_SCAN): ctl[0] the ticket counter (reset by
-// the block that takes the last ticket), ctl[1], ctl[2] the stamps of k_assign, status words from byte 256 on:
-// generation (30 bits) | state (2: 1 = block total, 2 = inclusive prefix) | value (32) — a word of an earlier launch
-// carries an older generation and reads as "not there yet", so nothing is cleared between launches.
-// REZERO: the input is a build's bin counters in a KEEP_ZERO block: every counter is cleared as it is read.
-// flags != nullptr: the first block also writes the build's eight device flags (grid.hpp) from the stamps.
-// ----------------------------------------------------------------------------
-static std::atomic<unsigned> g_scan_gen{0};
-static unsigned next_scan_gen()
-{
-    unsigned g = (++g_scan_gen) & 0x3fffffffu;
-    if (g == 0) { // 2^30 launches: old status words could repeat a generation — start over from clean control blocks
-        reset_kept_blocks(Scope::KEEP_SCAN);
-        g = (++g_scan_gen) & 0x3fffffffu;
-    }
-    return g;
-}
-
-template <bool REZERO, int ITEMS = SCAN_ITEMS>
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_onepass(unsigned *__restrict__ in, int *__restrict__ out, int64_t n,
-                                                             unsigned *__restrict__ ctl, unsigned gen, int *__restrict__ flags)
-{
-    constexpr int SCAN_ITEMS = ITEMS; // (shadows the namespace constant: the body below is written for any multiple of four)
-    __shared__ unsigned s_blk, s_excl;
-    unsigned long long *status = reinterpret_cast<unsigned long long *>(ctl + 64);
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid == 0) s_blk = atomicAdd(&ctl[0], 1u);
-    __syncthreads();
-    const unsigned blk = s_blk, nblk = gridDim.x;
-    if (tid == 0) {
-        if (blk == nblk - 1) ctl[0] = 0; // every ticket has been taken: ready for the next launch
-        if (blk == 0 && flags) {
-            flags[0] = ctl[1] == gen ? 1 : 0; flags[1] = 0; flags[2] = 0; flags[3] = 0;
-            flags[4] = ctl[2] == gen ? 1 : 0; flags[5] = 0; flags[6] = 0; flags[7] = 0;
-        }
-    }
-    const int64_t base = ((int64_t)blk * SCAN_BLOCK + tid) * SCAN_ITEMS;
-    unsigned v[SCAN_ITEMS], s = 0;
-    const bool vec = base + SCAN_ITEMS <= n && ((reinterpret_cast<uintptr_t>(in + base) | reinterpret_cast<uintptr_t>(out + base)) & 15u) == 0;
-    if (vec) {
-#pragma unroll
-        for (int c = 0; c < SCAN_ITEMS / 4; ++c) {
-            const uint4 q = reinterpret_cast<const uint4 *>(in + base)[c];
-            v[4 * c] = q.x; v[4 * c + 1] = q.y; v[4 * c + 2] = q.z; v[4 * c + 3] = q.w;
-        }
-        if (REZERO) {
-#pragma unroll
-            for (int c = 0; c < SCAN_ITEMS / 4; ++c) reinterpret_cast<uint4 *>(in + base)[c] = make_uint4(0u, 0u, 0u, 0u);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) {
-            v[k] = (base + k < n) ? in[base + k] : 0u;
-            if (REZERO && base + k < n) in[base + k] = 0u;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) s += v[k];
-    unsigned tot;
-    unsigned ex = block_excl_scan(s, &tot);
-    const unsigned long long stamp = (unsigned long long)gen << 34;
-    if (tid == 0) // this block's total (block 0: its inclusive prefix) for the blocks behind it
-        __hip_atomic_store(&status[blk], stamp | ((unsigned long long)(blk == 0 ? 2u : 1u) << 32) | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < 64) {
-        unsigned excl = 0;
-        if (blk > 0) {
-            int64_t j = (int64_t)blk - 1; // nearest predecessor
-            for (;;) {
-                const int64_t idx = j - lane;
-                unsigned long long st;
-                for (;;) {
-                    st = idx >= 0 ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (stamp | (2ull << 32));
-                    const bool there = (st >> 34) == gen && ((st >> 32) & 3u) != 0;
-                    if (__all(there))
-                        break;
-                    __builtin_amdgcn_s_sleep(2);
-                }
-                const unsigned long long pm = __ballot(((st >> 32) & 3u) == 2u);
-                const int first = pm ? __builtin_ctzll(pm) : 64; // nearest block that already knows its inclusive prefix
-                unsigned val = lane <= first ? (unsigned)(st & 0xffffffffull) : 0u;
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) val += __shfl_xor(val, d, 64);
-                excl += val;
-                if (pm)
-                    break;
-                j -= 64;
-            }
-            if (lane == 0)
-                __hip_atomic_store(&status[blk], stamp | (2ull << 32) | (unsigned long long)(excl + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) s_excl = excl;
-    }
-    __syncthreads();
-    ex += s_excl;
-    if (vec) {
-#pragma unroll
-        for (int c = 0; c < SCAN_ITEMS / 4; ++c) {
-            int4 o;
-            o.x = (int)ex; o.y = (int)(ex + v[4 * c]); o.z = (int)(ex + v[4 * c] + v[4 * c + 1]); o.w = (int)(ex + v[4 * c] + v[4 * c + 1] + v[4 * c + 2]);
-            reinterpret_cast<int4 *>(out + base)[c] = o;
-            ex += v[4 * c] + v[4 * c + 1] + v[4 * c + 2] + v[4 * c + 3];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; ++k) {
-            if (base + k < n) out[base + k] = (int)ex;
-            ex += v[k];
-        }
-    }
-    if (blk == nblk - 1 && tid == 0) out[n] = (int)(s_excl + tot); // grand total
-}
-
-static size_t scan_ctl_bytes(int64_t n)
-{
-    const int64_t per = (int64_t)SCAN_BLOCK * SCAN_ITEMS;
-    return 256 + (size_t)((n + per - 1) / per) * 8;
-}
-// out[0..n] = exclusive prefix of in[0..n), out[n] = total; rezero: clear in[] on the way (bin counters of a kept block)
-static void launch_scan_gen(hipStream_t st, unsigned *in, int *out, int64_t n, unsigned *ctl, unsigned gen, bool rezero, int *flags)
-{
-    const bool big = n >= SCAN_BIG_FROM;
-    const int64_t per = (int64_t)SCAN_BLOCK * (big ? SCAN_ITEMS_BIG : SCAN_ITEMS);
-    const dim3 grid((unsigned)std::max<int64_t>(1, (n + per - 1) / per)), block(SCAN_BLOCK);
-    if (big) {
-        if (rezero) hipLaunchKernelGGL((k_scan_onepass<true, SCAN_ITEMS_BIG>), grid, block, 0, st, in, out, n, ctl, gen, flags);
-        else hipLaunchKernelGGL((k_scan_onepass<false, SCAN_ITEMS_BIG>), grid, block, 0, st, in, out, n, ctl, gen, flags);
-    } else {
-        if (rezero) hipLaunchKernelGGL((k_scan_onepass<true, SCAN_ITEMS>), grid, block, 0, st, in, out, n, ctl, gen, flags);
-        else hipLaunchKernelGGL((k_scan_onepass<false, SCAN_ITEMS>), grid, block, 0, st, in, out, n, ctl, gen, flags);
-    }
-}
-static void launch_scan(hipStream_t st, unsigned *in, int *out, int64_t n, unsigned *ctl, bool rezero, int *flags)
-{
-    launch_scan_gen(st, in, out, n, ctl, next_scan_gen(), rezero, flags);
-}
-
-// out[0..n] = exclusive prefix sums of in[0..n) (out[n] = total); for other translation units (grid.hpp)
-int exclusive_scan_u32(Scope &sc, const unsigned *in, int *out, int64_t n)
-{
-    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(n), Scope::KEEP_SCAN));
-    if (sc.failed())
-        return sc.error();
-    launch_scan(sc.stream(), const_cast<unsigned *>(in), out, n, ctl, false, nullptr);
-    MDH_HIP(hipGetLastError());
-    return MDH_OK;
-}
-
-// ent: (cell, slot inside the cell) of every atom, one 8-byte entry from k_assign.  Two atoms per thread: their entries are ONE
-// 16-byte load: 31.9 us at 10 M atoms (8-byte loads run at 0.54-0.70 of the 16-byte rate: one atom per thread took 40.7 us, the two
-// separate arrays of ints before that 37.0; profiles/assign_window.md)
-__global__ __launch_bounds__(256) void k_scatter(const int2 *__restrict__ ent, const int *__restrict__ cell_start,
-                                                 int *__restrict__ order, int64_t N)
-{
-    const int64_t i = 2 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= N)
-        return;
-    int4 e; // (ent is 256-byte aligned and i is even: the pair is 16-byte aligned)
-    if (i + 1 < N) e = *reinterpret_cast<const int4 *>(ent + i);
-    else { const int2 last = ent[i]; e = make_int4(last.x, last.y, -1, 0); }
-    if (e.x >= 0) // (< 0: an absent atom, or one outside a promised cell window, k_assign)
-        order[cell_start[e.x] + e.y] = (int)i;
-    if (e.z >= 0)
-        order[cell_start[e.z] + e.w] = (int)(i + 1);
-}
-
-// The atomic counters hand out slots in arbitrary order; put every cell's
-// atoms into DESCENDING id order (what a walk of the reference's linked list
-// sees, neighbor.cpp:97-98) so that rows come out in reference order and the
-// result is deterministic.  One thread per cell; cells hold a handful of atoms.
-// key != nullptr: descending key[id] instead of descending id (a decomposed system: key = global atom id, so that the rows of
-// a slab come out in the order the whole system's rows have)
-// Cells of up to eight atoms (nearly all of them at cell width rc) are sorted in registers: the ids, then the keys, loaded as
-// one batch, a sorting network with fixed indices, the ids stored back.  The insertion sort below — every comparison a
-// dependent read of order[] and, with a key, of key[order[]] — was a chain of 6-10 memory latencies per cell: 32 us of the
-// headline build, 77 us of a slab's (random 8-byte key reads).
-template <int W, typename K>
-__device__ __forceinline__ void sort_cell_net(int *__restrict__ order, int s, int n, const int64_t *__restrict__ key)
-{
-    int id[W];
-    K k[W];
-#pragma unroll
-    for (int u = 0; u < W; ++u) id[u] = order[s + min(u, n - 1)];
-#pragma unroll
-    for (int u = 0; u < W; ++u) {
-        const K v = key ? (K)key[id[u]] : (K)id[u];
-        k[u] = u < n ? v : (sizeof(K) == 8 ? (K)INT64_MIN : (K)INT32_MIN); // pads sink to the end (descending order)
-    }
-    auto ce = [&](int a, int b) { // k[a] >= k[b] afterwards
-        const bool sw = k[a] < k[b];
-        const K ka = sw ? k[b] : k[a], kb = sw ? k[a] : k[b];
-        const int ia = sw ? id[b] : id[a], ib = sw ? id[a] : id[b];
-        k[a] = ka; k[b] = kb; id[a] = ia; id[b] = ib;
-    };
-    if (W == 4) {
-        ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2);
-    } else { // Batcher's odd-even merge sort of eight
-        ce(0, 1); ce(2, 3); ce(4, 5); ce(6, 7);
-        ce(0, 2); ce(1, 3); ce(4, 6); ce(5, 7);
-        ce(1, 2); ce(5, 6);
-        ce(0, 4); ce(1, 5); ce(2, 6); ce(3, 7);
-        ce(2, 4); ce(3, 5);
-        ce(1, 2); ce(3, 4); ce(5, 6);
-    }
-#pragma unroll
-    for (int u = 0; u < W; ++u)
-        if (u < n) order[s + u] = id[u];
-}
-
-// tmp: N ints of scratch indexed like `order` (the entries of k_assign, free once the atoms are scattered), for cells of
-// more than eight atoms without a key: the ids are copied there and every atom is PLACED at the number of larger ids of its
-// cell — n^2 independent, cached reads instead of the insertion sort's chain of dependent ones (dense cells, rc = 5 A: 11 atoms
-// per cell, up to 50 in the fat last cells: 239 -> 204 us at 10 M atoms, 131 -> 94 us at 3.4 M)
-__global__ __launch_bounds__(256) void k_sort_cells(const int *__restrict__ cell_start, int *__restrict__ order,
-                                                    int64_t ncell, const int64_t *__restrict__ key, int *__restrict__ tmp)
-{
-    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncell)
-        return;
-    const int s = cell_start[c], e = cell_start[c + 1];
-    const int n = e - s;
-    if (n <= 1)
-        return;
-    if (n <= 4) {
-        if (key) sort_cell_net<4, int64_t>(order, s, n, key);
-        else sort_cell_net<4, int>(order, s, n, nullptr);
-        return;
-    }
-    if (n <= 8) {
-        if (key) sort_cell_net<8, int64_t>(order, s, n, key);
-        else sort_cell_net<8, int>(order, s, n, nullptr);
-        return;
-    }
-    if (!key && tmp) {
-        for (int a = s; a < e; ++a) tmp[a] = order[a];
-        for (int a = s; a < e; ++a) {
-            const int mine = tmp[a];
-            int larger = 0;
-            for (int q = s; q < e; ++q) larger += tmp[q] > mine ? 1 : 0;
-            order[s + larger] = mine; // (ids are distinct: every slot of the cell is written once)
-        }
-        return;
-    }
-    for (int a = s + 1; a < e; ++a) {
-        int v = order[a], q = a - 1;
-        const int64_t kv = key ? key[v] : (int64_t)v;
-        while (q >= s && (key ? key[order[q]] : (int64_t)order[q]) < kv) {
-            order[q + 1] = order[q];
-            --q;
-        }
-        order[q + 1] = v;
-    }
-}
-
-// The same order for grids of many atoms per cell (N / ncell > 6: rc = 5 A in a metal, 11 atoms per cell): EIGHT lanes per cell.
-// The cell's ids are staged in LDS (64 per cell; a fuller cell is sorted by its first lane as above), then lane l
-// ranks the atoms l, l + 8, ... by counting the larger ids of its cell — n / 8 trips of n LDS reads instead of n * n dependent
-// global ones in a single lane (rc = 6 A, 18 atoms per cell, 4 M atoms: 240 us, as long as k_assign, k_scatter and k_gather together).
-constexpr int SORT_DENSE_CAP = 64;
-__global__ __launch_bounds__(256) void k_sort_cells_dense(const int *__restrict__ cell_start, int *__restrict__ order, int64_t ncell,
-                                                          int *__restrict__ tmp)
-{
-    __shared__ int ids[32 * SORT_DENSE_CAP];
-    const int sub = threadIdx.x & 7, lc = threadIdx.x >> 3;
-    const int64_t c = (int64_t)blockIdx.x * 32 + lc;
-    int s = 0, n = 0;
-    if (c < ncell) {
-        s = cell_start[c];
-        n = cell_start[c + 1] - s;
-    }
-    const bool staged = n > 1 && n <= SORT_DENSE_CAP, big = n > SORT_DENSE_CAP;
-    if (staged)
-        for (int a = sub; a < n; a += 8) ids[lc * SORT_DENSE_CAP + a] = order[s + a];
-    // a fuller cell — the LAST cell of an axis takes the remainder of the box (neighbor.cpp:58-61) and is up to twice as wide: the
-    // corner cell of a 256 k-atom box at rc = 5 A holds 84 atoms where the mean is 12 — goes through the free entries of k_assign instead,
-    // still eight lanes to the cell (one lane, n * n loads: 330 us for that one cell, as long as the rest of the call)
-    if (big)
-        for (int a = sub; a < n; a += 8) tmp[s + a] = order[s + a];
-    __syncthreads(); // (workgroup scope: the copies in LDS and in HBM are visible to the cell's other lanes)
-    if (staged) {
-        for (int a = sub; a < n; a += 8) {
-            const int mine = ids[lc * SORT_DENSE_CAP + a];
-            int larger = 0;
-            for (int q = 0; q < n; ++q) larger += ids[lc * SORT_DENSE_CAP + q] > mine ? 1 : 0;
-            order[s + larger] = mine; // (ids are distinct: every slot of the cell is written once)
-        }
-    } else if (big) {
-        for (int a = sub; a < n; a += 8) {
-            const int mine = tmp[s + a];
-            int larger = 0;
-            for (int q = 0; q < n; ++q) larger += tmp[s + q] > mine ? 1 : 0;
-            order[s + larger] = mine;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gather(const double *__restrict__ x, const double *__restrict__ y,
-                                                const double *__restrict__ z, const int *__restrict__ order,
-                                                double *__restrict__ xs, double *__restrict__ ys,
-                                                double *__restrict__ zs, int64_t N,
-                                                const unsigned short *__restrict__ mv, unsigned short *__restrict__ mvs,
-                                                CellGrid::Packed *__restrict__ pk, const int *__restrict__ any_code,
-                                                const int *__restrict__ n_binned)
-{
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N)
-        return;
-    if (n_binned && p >= *n_binned) // a windowed build that dropped atoms outside its window: order[] ends at the atoms binned
-        return;
-    const int i = order[p];
-
-    const double a = x[i], b = y[i], c = z[i];
-    // the image codes are a fourth scattered read per atom (one byte each); k_assign says whether any of them is not neutral
-    const unsigned short m = *any_code ? mv[i] : (unsigned short)img::ATOM_NEUTRAL;
-    if (pk) {
-        pk[p] = CellGrid::Packed{a, b, c, i, (int)m};
-        return;
-    }
-    xs[p] = a;
-    ys[p] = b;
-    zs[p] = c;
-    mvs[p] = m;
-}
-
-// the gather of scattered input: whole records (written in input order by k_assign), one random 32-byte read per atom
-__global__ __launch_bounds__(256) void k_gather_records(const CellGrid::Packed *__restrict__ rec, const int *__restrict__ order,
-                                                        CellGrid::Packed *__restrict__ pk, int64_t N, const int *__restrict__ n_binned)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N || p >= *n_binned)
-        return;
-    pk[p] = rec[order[p]];
-}
-
-__global__ __launch_bounds__(256) void k_unpack(const CellGrid::Packed *__restrict__ pk, int64_t N, double *__restrict__ xs,
-                                                double *__restrict__ ys, double *__restrict__ zs, unsigned short *__restrict__ mvs)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= N)
-        return;
-    const CellGrid::Packed r = pk[p];
-    xs[p] = r.x; ys[p] = r.y; zs[p] = r.z; mvs[p] = (unsigned short)r.code;
-}
-
-int ensure_unpacked(Scope &sc, CellGrid &cg, int64_t N)
-{
-    if ((!cg.pk && !cg.ix) || cg.xs)
-        return MDH_OK;
-    cg.xs = sc.alloc_n<double>((size_t)N);
-    cg.ys = sc.alloc_n<double>((size_t)N);
-    cg.zs = sc.alloc_n<double>((size_t)N);
-    cg.mvs = sc.alloc_n<unsigned short>((size_t)N);
-    if (sc.failed())
-        return sc.error();
-    if (cg.pk) // from the records
-        hipLaunchKernelGGL(k_unpack, dim3(grid_for(N, 256)), dim3(256), 0, sc.stream(), cg.pk, N, cg.xs, cg.ys, cg.zs, cg.mvs);
-    else // an indirect grid: the gather its build left out
-        hipLaunchKernelGGL(k_gather, dim3(grid_for(N, 256)), dim3(256), 0, sc.stream(), cg.ix, cg.iy, cg.iz, cg.order, cg.xs, cg.ys, cg.zs, N, cg.imv,
-                           cg.mvs, (CellGrid::Packed *)nullptr, cg.flags + 4, cg.cell_start + cg.g.ncell);
-    MDH_HIP(hipGetLastError());
-    return MDH_OK;
-}
-
-// ----------------------------------------------------------------------------
-// Cell window (decomposed systems).  A rank's atoms — its slab and the halo — occupy a few planes of the GLOBAL cell grid the
-// neighbor build works on (global box, global cells: the rows equal the undivided system's), and the passes over ALL cells
-// (bin counters zeroed, three scan kernels, the in-cell sort) then cost more than the passes over the atoms.  The caller, who
-// knows where its atoms are, promises a window of fractional coordinates along one axis (mdh_hint_cell_window, consumed by
-// the next build on this thread); those passes run over the window's planes (one more on each side) only, and the prefix
-// array outside them is filled with the constants a full scan would have left there, so that every reader of cell_start is
-// served as before.  An atom binned outside the promised window breaks the promise: counted on the device, reported by
-// the next call of this thread that builds a grid.
-// ----------------------------------------------------------------------------
-struct CellWindow { int axis; double lo, hi; bool set; };
-static thread_local CellWindow g_window{0, 0.0, 0.0, false};
-// ... and inside the window the stretch that holds the atoms whose rows are wanted (mdh_hint_centre_window: a rank's OWN slab; what
-// lies between it and the window's ends are ghosts — candidates of the tile kernel, never its centres: their rows are not made)
-static thread_local CellWindow g_centre{0, 0.0, 0.0, false};
-static thread_local int *g_window_violations = nullptr; // pinned host word of the previous windowed build
-
-// out[a..b) = *v (a value that is on the device only)
-// (16-byte stores over the aligned middle — the region behind a slab's window is most of the global grid, 100 MB on eight ranks —
-// launched by fill_from() below)
-__global__ __launch_bounds__(256) void k_fill_from(int *__restrict__ out, int64_t a, int64_t b, const int *__restrict__ v)
-{
-    const int val = *v;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b - a < 8) {
-        if (a + i < b) out[a + i] = val;
-        return;
-    }
-    const int64_t a4 = (a + 3) & ~(int64_t)3, b4 = b & ~(int64_t)3; // a4 <= b4: out is 16-byte aligned at multiples of four
-    const int64_t q = a4 + 4 * i;
-    if (q + 4 <= b4) *reinterpret_cast<int4 *>(out + q) = make_int4(val, val, val, val);
-    if (i < 4) {
-        if (a + i < a4) out[a + i] = val;
-        if (b4 + i < b) out[b4 + i] = val;
-    }
-}
-// a one-piece window [a0, a1] of the grid: zeros in front of it, *v (the atoms binned, cell_start[a1]) behind it — ONE launch behind
-// the window's scan instead of a memset in front of it and a fill behind (a memset is two 5 us nodes on the stream)
-__global__ __launch_bounds__(256) void k_fill_outside(int *__restrict__ out, int64_t a0, int64_t a1, int64_t n1, const int *__restrict__ v)
-{
-    const int val = *v;
-    const int64_t q = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-    const int64_t head4 = (a0 + 3) >> 2 << 2;               // the head [0, a0) rounded up to whole quads (the overshoot is fixed below)
-    const int64_t t0 = (a1 + 1 + 3) & ~(int64_t)3;          // first aligned index behind the window
-    if (q < head4) {
-        if (q + 4 <= a0) *reinterpret_cast<int4 *>(out + q) = make_int4(0, 0, 0, 0);
-        else for (int64_t i = q; i < a0; ++i) out[i] = 0;
-        return;
-    }
-    const int64_t r = q - head4 + t0;                       // quads behind the window
-    if (r == t0) for (int64_t i = a1 + 1; i < t0 && i < n1; ++i) out[i] = val;
-    if (r + 4 <= n1) *reinterpret_cast<int4 *>(out + r) = make_int4(val, val, val, val);
-    else for (int64_t i = r; i < n1; ++i) out[i] = val;
-}
-static void fill_from(hipStream_t st, int *out, int64_t a, int64_t b, const int *v)
-{
-    if (b > a)
-        hipLaunchKernelGGL(k_fill_from, dim3(grid_for((b - a) / 4 + 8, 256)), dim3(256), 0, st, out, a, b, v);
-}
-
-// out[a..b) += *v  (v outside [a, b)); the entry `skip`, if in range, is left alone
-__global__ __launch_bounds__(256) void k_add_from(int *__restrict__ out, int64_t a, int64_t b, const int *__restrict__ v, int64_t skip)
-{
-    const int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < b && i != skip) out[i] += *v;
-}
-
-// atoms binned outside planes [p0, p1) u [p2, p3) of axis 0 (cells are a0-major)
-int neighbor_grid_dims(const DBox &b, double rc, Grid &g)
-{
-    double nc_total = 1.0;
-    for (int d = 0; d < 3; ++d) { // neighbor.cpp:203-206
-        double f = std::floor(b.thick[d] / rc);
-        if (!(f < 2147483647.0)) { set_error("cell grid too large (box thickness / rc overflows int)"); return MDH_ERR_ARG; }
-        int n = (int)f;
-        g.nc[d] = n > 3 ? n : 3;
-        nc_total *= (double)g.nc[d];
-    }
-    if (nc_total > 2147483000.0) {
-        set_error("cell grid too large: " + std::to_string(nc_total) + " cells (the reference indexes cells with int32)");
-        return MDH_ERR_ARG;
-    }
-    g.ncell = (int64_t)g.nc[0] * g.nc[1] * g.nc[2];
-    g.rc_inv = 1.0 / rc; // neighbor.cpp:78
-    g.mode = 0;
-    return MDH_OK;
-}
-
-// Do the atoms come in a spatial order?  One workgroup samples 1 024 pairs of consecutive atoms (i, i+1): far = more than two
-// bins of ~64 atoms apart along some axis (fractional coordinates, periodic axes wrapped); more than a quarter far -> *flag = 1 (a word
-// of pinned host memory, order_hint()): the NEXT builds of this (N, grid) move whole 32-byte records (k_assign writes them in input
-// order, the gather reads one random sector per atom instead of three or four: 598 -> ~250 us at 10 M shuffled atoms).  A lattice
-// builder's order, a file written cell by cell, a sorted copy: 0.  Launched on the first and every eighth build of a signature.
-__global__ __launch_bounds__(1024) void k_order_far_flag(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
-                                                         int64_t N, DBox b, double nb0, double nb1, double nb2, int *__restrict__ flag)
-{
-    __shared__ int s_far;
-    if (threadIdx.x == 0) s_far = 0;
-    __syncthreads();
-    const int64_t step = (N - 1) / 1024 > 0 ? (N - 1) / 1024 : 1;
-    const int64_t i = (int64_t)threadIdx.x * step;
-    bool far = false;
-    if (i + 1 < N) {
-        const double dx = x[i + 1] - x[i], dy = y[i + 1] - y[i], dz = z[i + 1] - z[i];
-        double f[3] = {dx * b.hi[0] + dy * b.hi[3] + dz * b.hi[6], dx * b.hi[1] + dy * b.hi[4] + dz * b.hi[7], dx * b.hi[2] + dy * b.hi[5] + dz * b.hi[8]};
-        const double nb[3] = {nb0, nb1, nb2};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (b.pbc[d]) f[d] -= rint(f[d]);
-            far = far || !(fabs(f[d]) * nb[d] <= 2.0); // (NaN counts as far)
-        }
-    }
-    const unsigned long long m = __ballot(far);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_far, __popcll(m));
-    __syncthreads();
-    if (threadIdx.x == 0) *flag = 4 * s_far > 1024 ? 1 : 0;
-}
-
-int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b,
-                    bool wrap_first, bool sort_desc, CellGrid &cg, const int64_t *sort_key, bool packed, bool scattered)
-{
-    const Grid &g = cg.g;
-    hipStream_t st = sc.stream();
-
-    // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
-    // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
-    unsigned *cell_count = static_cast<unsigned *>(sc.alloc_kept(sizeof(unsigned) * (size_t)g.ncell, Scope::KEEP_ZERO));
-    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
-    cg.flags = sc.alloc_n<int>(8);
-    cg.cell_start = sc.alloc_n<int>((size_t)g.ncell + 1);
-    int2 *ent = sc.alloc_n<int2>((size_t)N); // (cell, slot) of every atom: k_assign -> k_scatter
-    int *rank = reinterpret_cast<int *>(ent); // ... and, once the atoms are scattered, the N ints of scratch of the in-cell sorts
-    cg.order = sc.alloc_n<int>((size_t)N + 4); // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
-    unsigned short *mv = sc.alloc_n<unsigned short>((size_t)N);
-    cg.xs = cg.ys = cg.zs = nullptr;
-    cg.mvs = nullptr;
-    cg.pk = nullptr;
-    // scattered (with packed): the caller knows that the atoms come in no spatial order
-    CellGrid::Packed *rec = nullptr;
-    int *rec_flag = nullptr;
-    cg.ix = cg.iy = cg.iz = nullptr;
-    cg.imv = nullptr;
-    if (packed) {
-        // records: always for a caller that knows (scattered); for a large system otherwise when the last sample of this (N, grid) said so
-        if (!scattered && N >= (int64_t(1) << 18)) {
-            const OrderHint h = order_hint(1, N, g.ncell, x);
-            scattered = h.word && *(volatile int *)h.word != 0;
-            if (h.word && h.sample) rec_flag = h.word;
-        }
-        // input in some spatial order: no sorted copy, the kernels read through `order` (CellGrid::ix); MDH_INDIRECT=0 /
-        // mdh_debug_set_indirect(0): the records always — an A/B switch, and how the tests reach both paths on one input
-        // (not for dense cells — six atoms and more, the wide instance's ground: two workgroups per CU hide the staging's
-        // dependent gathers badly, build_neighbor(5.0, 50) at 10 M atoms 4.48 -> 4.60 ms; profiles/r06_cell_grid_ab.txt)
-        const bool indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && sort_desc && (double)N <= 6.0 * (double)g.ncell && g_next_rows <= 16;
-        g_next_rows = 0;
-        if (!indirect) cg.pk = sc.alloc_n<CellGrid::Packed>((size_t)N);
-        if (scattered) rec = sc.alloc_n<CellGrid::Packed>((size_t)N);
-    } else {
-        cg.xs = sc.alloc_n<double>((size_t)N);
-        cg.ys = sc.alloc_n<double>((size_t)N);
-        cg.zs = sc.alloc_n<double>((size_t)N);
-        cg.mvs = sc.alloc_n<unsigned short>((size_t)N);
-    }
-    if (sc.failed())
-        return sc.error();
-
-    // window of planes along axis 0 (orthogonal boxes, rc-wide cells): [p0, p1) and, when it wraps around the ring, [p2, p3)
-    int p0 = 0, p1 = g.nc[0], p2 = 0, p3 = 0;
-    bool windowed = false;
-    if (g_window_violations && *(volatile int *)g_window_violations != 0) {
-        *g_window_violations = 0;
-        g_window.set = false;
-        set_error("an earlier neighbor build on this thread found atoms outside the cell window it had been promised (mdh_hint_cell_window)");
-        return MDH_ERR_ARG;
-    }
-    if (g_window.set) {
-        const CellWindow w = g_window;
-        g_window.set = false; // one build
-        // (only the neighbor builds — the callers of the packed record — know what a window leaves undone; a hint that meets
-        // any other grid build is dropped)
-        if (packed && w.axis == 0 && !b.tri && g.mode == 0 && g.nc[0] >= 16 && w.hi > w.lo && w.hi - w.lo < 0.75) {
-            const double L = b.h[0];
-            int lo = (int)std::floor(w.lo * L * g.rc_inv) - 1, hi = (int)std::ceil(w.hi * L * g.rc_inv) + 1; // one plane of margin
-            if (hi - lo < g.nc[0] - 2) {
-                windowed = true;
-                if (lo < 0) { p0 = 0; p1 = std::min(hi, g.nc[0]); p2 = g.nc[0] + lo; p3 = g.nc[0]; }         // wraps below
-                else if (hi > g.nc[0]) { p0 = 0; p1 = hi - g.nc[0]; p2 = lo; p3 = g.nc[0]; }                   // wraps above
-                else { p0 = lo; p1 = hi; p2 = p3 = 0; }
-                if (p2 < p1 && p3 > p2) { windowed = false; p0 = 0; p1 = g.nc[0]; p2 = p3 = 0; }               // (the pieces meet: everything)
-            }
-        }
-    }
-    const int64_t plane = (int64_t)g.nc[1] * g.nc[2];
-    cg.win_lo = cg.win_hi = 0;
-    if (windowed && p3 <= p2) { cg.win_lo = p0; cg.win_hi = p1; } // one piece: the tile kernel runs over its range of tiles
-    cg.cen_lo = cg.cen_hi = 0;
-    if (g_centre.set) {
-        const CellWindow c = g_centre;
-        g_centre.set = false; // one build
-        if (packed && c.axis == 0 && !b.tri && g.mode == 0 && c.hi > c.lo && c.lo >= 0.0 && c.hi <= 1.0) {
-            // the planes an atom of fraction [lo, hi) can be binned into (cell_coords: floor((x - o) rc_inv), clamped); the ends moved
-            // out by 1e-9 of their value — far more than the roundings that separate the caller's fraction of an atom from the grid's
-            // (x - o) rc_inv, far less than a plane: an atom ON the slab's face is inside whichever way it was rounded
-            const double L = b.h[0];
-            cg.cen_lo = std::max(0, std::min(g.nc[0] - 1, (int)std::floor(c.lo * L * g.rc_inv * (1.0 - 1e-9) - 1e-9)));
-            cg.cen_hi = std::min(g.nc[0], (int)std::floor(c.hi * L * g.rc_inv * (1.0 + 1e-9) + 1e-9) + 1);
-        }
-    }
-    cg.flags_fresh = true;
-    // slack for the raw-vs-wrapped consistency flag: far above rounding, far below a cell width
-    const double slack = 0.01 / (g.rc_inv > 0 ? g.rc_inv : 1.0);
-    // the promise is checked where the atoms are binned (a word of pinned host memory the kernel writes) and read by the next
-    // build of this thread or by mdh_cell_window_check
-    CellPlanes win{p0, p1, p2, p3, nullptr};
-    if (windowed) {
-        if (!g_window_violations) MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&g_window_violations), sizeof(int), hipHostMallocDefault));
-        *g_window_violations = 0;
-        win.bad = g_window_violations;
-    }
-    if (rec_flag) {
-        const double *h = b.h;
-        const double vol = std::fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]));
-        const double edge = std::cbrt(64.0 * vol / (double)N);
-        double nb[3];
-        for (int d = 0; d < 3; ++d) nb[d] = std::max(1.0, std::floor(b.thick[d] / edge));
-        hipLaunchKernelGGL(k_order_far_flag, dim3(1), dim3(1024), 0, st, x, y, z, N, b, nb[0], nb[1], nb[2], rec_flag);
-    }
-    const unsigned gen = next_scan_gen(); // stamps of this build's k_assign; the (first) scan below is launched with the same value
-    // atoms per lane: four; small systems keep one atom per lane (they need the workgroups to fill the chip)
-    // (measured at 10 M atoms, with the grouping of round 5 — runs of adjacent lanes: 145 -> 120 us on a lattice, 162 -> 162 on a polycrystal — 10 M runs of one atom, the atomics' own
-    // throughput — 413 -> 440 on a shuffled frame, which therefore keeps one: profiles/r05_assign_k.txt)
-    const bool assign4 = N >= (int64_t)1 << 20 && !scattered;
-#define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)wrap_first, ent, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
-    if (b.tri) {
-        if (assign4) MDH_ASSIGN(true, 4); else MDH_ASSIGN(true, 1);
-    } else {
-        if (assign4) MDH_ASSIGN(false, 4); else MDH_ASSIGN(false, 1);
-    }
-#undef MDH_ASSIGN
-    auto scan_piece = [&](int64_t from, int64_t to, unsigned use_gen, int *flags) {
-        launch_scan_gen(st, cell_count + from, cg.cell_start + from, to - from, ctl, use_gen, true, flags); // [to] = the piece's total
-    };
-    if (!windowed) {
-        scan_piece(0, g.ncell, gen, cg.flags);
-    } else {
-        // the pieces in index order: [p0, p1) then [p2, p3); a piece is scanned on its own, the atoms before it added by the
-        // fill / by a second add pass; cell_start elsewhere = what a full scan leaves: the atoms binned so far.  The counters
-        // outside the window are zero (kept block; atoms out there take no slot) and stay untouched.
-        const int64_t a0 = p0 * plane, a1 = p1 * plane, b0 = p2 * plane, b1 = p3 * plane;
-        // (constant fills through the runtime's fill kernel: 16-byte stores, 5 us per 10 MB against 15 of a store per thread)
-        hipError_t fill_err = hipSuccess;
-        auto fill_const = [&](int64_t from, int64_t to, int v) {
-            if (to > from && fill_err == hipSuccess)
-                fill_err = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cg.cell_start + from), v, (size_t)(to - from), st);
-        };
-        if (b1 > b0) fill_const(0, a0, 0);
-        // (from a multiple of four cells on: the scan moves 16 bytes per access only from an aligned start — 66 against 26 us for the
-        // 3.6 M cells of a 10 M-atom slab; the up to three counters in front of the window are zero, and zero is what the cells in
-        // front of the window hold)
-        scan_piece(a0 & ~(int64_t)3, a1, gen, cg.flags);
-        if (b1 <= b0) { // one piece: everything outside it in one launch
-            const int64_t n1 = g.ncell + 1, quads = ((a0 + 3) >> 2) + ((n1 - std::min(n1, (a1 + 1 + 3) & ~(int64_t)3) + 3) >> 2) + 1;
-            hipLaunchKernelGGL(k_fill_outside, dim3(grid_for(quads, 256)), dim3(256), 0, st, cg.cell_start, a0, a1, n1, cg.cell_start + a1);
-        } else if (b1 > b0) {
-            // second piece: offsets start at the first piece's total, which sits on the device in cell_start[a1]
-            fill_from(st, cg.cell_start, a1 + 1, b0, cg.cell_start + a1);
-            scan_piece(b0, b1, next_scan_gen(), nullptr);
-            hipLaunchKernelGGL(k_add_from, dim3(grid_for(b1 - b0 + 1, 256)), dim3(256), 0, st, cg.cell_start, b0, b1 + 1, cg.cell_start + a1, (int64_t)-1);
-            // behind the window: the number of atoms BINNED (cell_start[b1], on the device) — N unless the promise was broken; with
-            // the constant N a cell behind a broken window spanned the records [n_binned, N), which k_scatter / k_gather never wrote
-            if (b1 < g.ncell)
-                fill_from(st, cg.cell_start, b1 + 1, g.ncell + 1, cg.cell_start + b1);
-        }
-        MDH_HIP(fill_err);
-    }
-    sc.keep_confirm(cell_count); // every counter a binned atom touched has been read and cleared by a scan enqueued above
-    hipLaunchKernelGGL(k_scatter, dim3(grid_for((N + 1) / 2, 256)), dim3(256), 0, st, ent, cg.cell_start, cg.order, N);
-    if (sort_desc) {
-        if (!windowed && !sort_key && (double)N > 6.0 * (double)g.ncell) {
-            hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rank);
-        } else if (!windowed) {
-            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, sort_key, rank);
-        } else {
-            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p1 - p0) * plane, 256)), dim3(256), 0, st, cg.cell_start + p0 * plane, cg.order, (p1 - p0) * plane, sort_key, rank);
-            if (p3 > p2)
-                hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p3 - p2) * plane, 256)), dim3(256), 0, st, cg.cell_start + p2 * plane, cg.order, (p3 - p2) * plane, sort_key, rank);
-        }
-    }
-    // (the atoms binned = the grid's total, on the device: all N unless absent atoms were handed in or a window's promise was broken)
-    const int *n_binned = cg.cell_start + g.ncell;
-    if (packed && !cg.pk) { cg.ix = x; cg.iy = y; cg.iz = z; cg.imv = mv; } // indirect: nothing is gathered
-    else if (rec) hipLaunchKernelGGL(k_gather_records, dim3(grid_for(N, 256)), dim3(256), 0, st, rec, cg.order, cg.pk, N, n_binned);
-    else hipLaunchKernelGGL(k_gather, dim3(grid_for(N, 256)), dim3(256), 0, st, x, y, z, cg.order, cg.xs, cg.ys, cg.zs, N, mv, cg.mvs, cg.pk, cg.flags + 4, n_binned);
-    MDH_HIP(hipGetLastError());
-    return MDH_OK;
-}
+int g_neighbor_variant = 0; // 0 = automatic, 1 = force the thread-per-atom kernel, any other value = no tile kernel of neighbor_lane.hip: the round-1 LDS-tiled kernel where it applies (tests pass 2)
 
 // ----------------------------------------------------------------------------
 // 27-cell scan, one thread per centre atom (centres taken in cell order so the
@@ -1275,51 +429,6 @@ __global__ __launch_bounds__(64) void k_sort_rows(int *__restrict__ verlet, doub
     }
 }
 
-// the round-2 form of the same (64 rows per workgroup, a lane to a row): kept for A/B measurements (mdh_debug_set_neighbor_variant(3))
-constexpr int SORT_ROWS = 64;
-__global__ __launch_bounds__(SORT_ROWS) void k_sort_rows_r2(int *__restrict__ verlet, double *__restrict__ dist, int64_t N,
-                                                            int64_t M, int k)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char sort_lds[];
-    double *ld = reinterpret_cast<double *>(sort_lds);            // [M][64]
-    int *lv = reinterpret_cast<int *>(ld + (size_t)M * SORT_ROWS); // [M][64]
-    const int64_t row0 = (int64_t)blockIdx.x * SORT_ROWS;
-    const int rows = (int)((N - row0) < SORT_ROWS ? (N - row0) : SORT_ROWS);
-    const int64_t total = (int64_t)rows * M;
-    const int t = threadIdx.x;
-    for (int64_t e = t; e < total; e += SORT_ROWS) {
-        const int r = (int)(e / M), c = (int)(e - (int64_t)r * M);
-        ld[c * SORT_ROWS + r] = dist[row0 * M + e];
-        lv[c * SORT_ROWS + r] = verlet[row0 * M + e];
-    }
-    __syncthreads();
-    bool moved = false;
-    if (t < rows) {
-        for (int a = 0; a < k; ++a) {
-            int best = a;
-            double db = ld[a * SORT_ROWS + t];
-            for (int c = a + 1; c < M; ++c) {
-                const double v = ld[c * SORT_ROWS + t];
-                if (v < db) { db = v; best = c; }
-            }
-            if (best != a) {
-                const double td = ld[a * SORT_ROWS + t];
-                ld[a * SORT_ROWS + t] = db; ld[best * SORT_ROWS + t] = td;
-                const int tv = lv[a * SORT_ROWS + t];
-                lv[a * SORT_ROWS + t] = lv[best * SORT_ROWS + t]; lv[best * SORT_ROWS + t] = tv;
-                moved = true;
-            }
-        }
-    }
-    if (!__syncthreads_or(moved ? 1 : 0))
-        return;
-    for (int64_t e = t; e < total; e += SORT_ROWS) {
-        const int r = (int)(e / M), c = (int)(e - (int64_t)r * M);
-        dist[row0 * M + e] = ld[c * SORT_ROWS + r];
-        verlet[row0 * M + e] = lv[c * SORT_ROWS + r];
-    }
-}
-
 // the same in place in HBM, for rows too wide for the LDS copy
 __global__ __launch_bounds__(256) void k_sort_rows_wide(int *__restrict__ verlet, double *__restrict__ dist, int64_t N,
                                                         int64_t M, int k)
@@ -1493,15 +602,16 @@ static int width_hint(int64_t N, int64_t ncell, int set)
     return 0;
 }
 
-// One pass over a built cell grid: mode 0 = counts only (nn, *dmax), 1 = reference semantics (caller's pads), 2 = pads written.
-// The tile kernel where it applies, the round-1 tiled kernel for cells too full for it, the thread-per-atom code for the rest.
-// pattern != nullptr (mode 1 or 2): fixed-cutoff CNA labels as well.  Fused into the tile kernel where that runs (the
-// leftovers of its mop-up kernels are listed in todo and labelled from the finished rows); *fused = false: nothing was
-// labelled, the caller runs the analysis on the lists
-static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N, double rc, int *dv, double *dd, int *dn,
-                         int64_t M, int mode, int *dmax, int *pattern = nullptr, int *todo = nullptr, bool *fused = nullptr)
+// One pass over a built cell grid (RowsRequest, grid.hpp).  The tile kernel where it applies, the round-1 tiled kernel for cells
+// too full for it, the thread-per-atom code for the rest.
+// labelled: the request's fixed-cutoff CNA labels were written by the tile kernel (the leftovers of its mop-up kernels are listed in
+// todo); false: nothing was labelled, the whole analysis runs on the finished rows (launch_labels)
+struct RowsDone { bool labelled = false; };
+static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N, double rc, const RowsRequest &rows, RowsDone &out)
 {
     hipStream_t st = sc.stream();
+    const bool count = rows.pads == RowsRequest::COUNT_ONLY;
+    out.labelled = false;
     if (!cg.flags_fresh) MDH_HIP(hipMemsetAsync(cg.flags + 2, 0, sizeof(int) * 2, st)); // the tile lists of this pass (flags[0], unwrapped input, stays)
     cg.flags_fresh = false;
     TileFilter tf{};
@@ -1509,50 +619,69 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
     if (g_neighbor_variant == 0) { // tile kernel (orthogonal and triclinic boxes); the thread-per-atom code below then only mops up what it listed
         GridStats gs;
         MDH_TRY(grid_stats_hint(sc, cg, N, &gs));
-        const bool cna = pattern && mode != 0;
-        const LanePlan lp = plan_lane(b, cg.g, N, mode == 0 ? 1 : M, gs, rc, cna, mode == 0);
+        const bool cna = rows.pattern && !count;
+        const LanePlan lp = plan_lane(b, cg.g, N, count ? 1 : rows.M, gs, rc, cna, count);
         if (lp.txy) {
-            if (cna) tf.cna_todo = todo;
-            MDH_TRY(launch_neighbor_lane(sc, cg, lp, N, b, rc, dv, dd, dn, mode == 0 ? 1 : M, mode == 2, mode == 0, dmax, tf, cna ? pattern : nullptr));
+            if (cna) tf.cna_todo = rows.todo;
+            MDH_TRY(launch_neighbor_lane(sc, cg, lp, N, b, rc, rows, tf));
             done = true;
-            if (cna && fused) *fused = true;
+            out.labelled = cna;
         }
     }
-    if (!done && mode != 0 && g_neighbor_variant != 1 && !b.tri) { // cells too full for the kernel above (or forced): the round-1 tiled kernel
+    if (!done && !count && g_neighbor_variant != 1 && !b.tri) { // cells too full for the kernel above (or forced): the round-1 tiled kernel
         int64_t occ = 0;
         MDH_TRY(occupied_cells_hint(sc, cg, N, &occ));
-        const TiledPlan plan = plan_tiled(b, cg.g, N, M, occ);
+        const TiledPlan plan = plan_tiled(b, cg.g, N, rows.M, occ);
         if (plan.tile) {
             MDH_TRY(ensure_unpacked(sc, const_cast<CellGrid &>(cg), N));
-            MDH_TRY(launch_neighbor_tiled(sc, cg, plan, N, b, rc, dv, dd, dn, M, mode == 2, tf));
+            MDH_TRY(launch_neighbor_tiled(sc, cg, plan, N, b, rc, rows, tf));
         }
     }
-    if (mode == 0) launch_neighbor<0>(st, cg, N, b, rc, nullptr, nullptr, dn, 1, dmax, tf);
-    else if (mode == 2) launch_neighbor<2>(st, cg, N, b, rc, dv, dd, dn, M, nullptr, tf);
-    else launch_neighbor<1>(st, cg, N, b, rc, dv, dd, dn, M, nullptr, tf);
+    if (count) launch_neighbor<0>(st, cg, N, b, rc, nullptr, nullptr, rows.nn, 1, rows.max_count, tf);
+    else if (rows.pads == RowsRequest::WRITE_PADS) launch_neighbor<2>(st, cg, N, b, rc, rows.verlet, rows.dist, rows.nn, rows.M, nullptr, tf);
+    else launch_neighbor<1>(st, cg, N, b, rc, rows.verlet, rows.dist, rows.nn, rows.M, nullptr, tf);
     if (g_moved_probe) // mdh_debug_track_counters(1): the build's "image codes not valid" flag, for mdh_debug_counters
         MDH_HIP(hipMemcpyAsync(g_moved_probe, cg.flags, sizeof(int), hipMemcpyDeviceToHost, st));
     MDH_HIP(hipGetLastError());
     return MDH_OK;
 }
 
-// For other units of the library (knn.hip): the rows of a cutoff build on device arrays — its own cell grid, pads written (-1 / rc + 1),
-// counts that keep running past M — enqueued on the Scope's stream.  ids_only: the caller does not read the distances (dd must still
-// be a buffer of N x M: the kernels for rows of <= 16 slots and the mop-up code write them regardless).
-void lane_ids_only(bool on); // neighbor_lane.hip
+// the grid of a build of neighbor rows of `row_width` slots (0: not known, or counting): atoms wrapped, cells in reference order
+static GridRequest rows_grid(const int64_t *key, int64_t row_width)
+{
+    GridRequest rq;
+    rq.wrap_first = rq.sort_desc = true; rq.sort_key = key; rq.atoms = GridRequest::FOR_ROWS;
+    rq.row_width = (int)std::min<int64_t>(row_width, 1 << 20);
+    return rq;
+}
+
+// The fixed-cutoff CNA labels behind a pass that was asked for them: of the atoms the tile kernel left on its to-do list where it
+// labelled its own centres, of all atoms from the finished rows otherwise.  done: the kept block todo sits in
+static int launch_labels(Scope &sc, const DBox &b, const double *dx, const double *dy, const double *dz, int64_t N, const RowsRequest &rows,
+                          double rc, int *done, const RowsDone &pass)
+{
+    ProfRange pr("k_fcna", sc.stream());
+    if (pass.labelled) launch_fcna_listed(sc.stream(), b, dx, dy, dz, N, rows.verlet, rows.M, rows.nn, rows.pattern, rc, rows.todo, done);
+    else launch_fcna_all(sc.stream(), b, dx, dy, dz, N, rows.verlet, rows.M, rows.nn, rows.pattern, rc, rows.todo, done);
+    MDH_HIP(hipGetLastError());
+    sc.keep_confirm(done); // (the list's walker leaves the counters zero)
+    return MDH_OK;
+}
+
+// grid.hpp
 int neighbor_rows_device(Scope &sc, const double *dx, const double *dy, const double *dz, int64_t N, const DBox &b, double rc, int *dv,
                          double *dd, int *dn, int64_t M, const int64_t *dkey, bool ids_only)
 {
     CellGrid cg;
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
-    g_next_rows = (int)std::min<int64_t>(M, 1 << 20);
-    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, dkey, true));
+    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rows_grid(dkey, M), cg));
     // pads written (the tile kernel then stores whole 16-byte groups; leaving the pads out measured SLOWER: 2.96 against 2.54 ms
     // at 10 M atoms, rc 3.8, 24 slots); distances wanted or not (rows of more than 16 slots: the wide instance skips them)
-    lane_ids_only(ids_only);
-    const int rcode = neighbor_pass(sc, cg, b, N, rc, dv, dd, dn, M, 2, nullptr);
-    lane_ids_only(false);
-    return rcode;
+    RowsRequest rows;
+    rows.verlet = dv; rows.dist = dd; rows.nn = dn; rows.M = M;
+    rows.pads = RowsRequest::WRITE_PADS; rows.ids_only = ids_only;
+    RowsDone pass;
+    return neighbor_pass(sc, cg, b, N, rc, rows, pass);
 }
 
 int moved_probe(int enable) // enable > 0: start tracking; 0: stop; < 0: the last value (-1: none)
@@ -1588,54 +717,37 @@ int mdh_build_neighbor_keyed(const double *x, const double *y, const double *z, 
                              const double *origin3, const int *boundary3, double rc, int *verlet, double *dist, int *nn,
                              int64_t max_neigh, int fill_pads, const int64_t *key, int space, void *stream)
 {
-    if (N < 0 || N >= 2147483647LL || !(rc > 0) || max_neigh <= 0) { set_error("mdh_build_neighbor: invalid N, rc or max_neigh"); return MDH_ERR_ARG; }
-    DBox b;
-    MDH_TRY(make_box(b, box9, origin3, boundary3));
-    if (N == 0)
-        return MDH_OK;
-    Scope sc(stream);
-    const double *dx = sc.stage_in(x, (size_t)N, space), *dy = sc.stage_in(y, (size_t)N, space), *dz = sc.stage_in(z, (size_t)N, space);
-    // host space + reference semantics: pads come from the caller's buffers, so they are uploaded too
-    int *dv = sc.stage(verlet, (size_t)(N * max_neigh), space, !fill_pads, true);
-    double *dd = sc.stage(dist, (size_t)(N * max_neigh), space, !fill_pads, true);
-    int *dn = sc.stage(nn, (size_t)N, space, false, true);
-    const int64_t *dkey = key ? sc.stage_in(key, (size_t)N, space) : nullptr;
-    if (sc.failed())
-        return sc.error();
-    CellGrid cg;
-    MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
-    {
-        ProfRange pr("cell_grid", sc.stream());
-        g_next_rows = (int)std::min<int64_t>(max_neigh, 1 << 20);
-        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, dkey, true));
-    }
-    {
-        ProfRange pr("k_neighbor", sc.stream());
-        MDH_TRY(neighbor_pass(sc, cg, b, N, rc, dv, dd, dn, max_neigh, fill_pads ? 2 : 1, nullptr));
-    }
-    return sc.finish(space);
+    return mdh_build_neighbor_fcna(x, y, z, N, box9, origin3, boundary3, rc, verlet, dist, nn, max_neigh, fill_pads, nullptr, key,
+                                   space, stream);
 }
 
-// mdh_build_neighbor followed by mdh_fcna with the same rc, in one pass over the tiles where the tile kernel applies
+// pattern (N) i32: mdh_build_neighbor followed by mdh_fcna with the same rc, in one pass over the tiles where the tile kernel
+// applies; NULL: the rows alone (the two entry points above)
 int mdh_build_neighbor_fcna(const double *x, const double *y, const double *z, int64_t N, const double *box9,
                             const double *origin3, const int *boundary3, double rc, int *verlet, double *dist, int *nn,
                             int64_t max_neigh, int fill_pads, int *pattern, const int64_t *key, int space, void *stream)
 {
-    if (N < 0 || N >= 2147483647LL || !(rc > 0) || max_neigh <= 0) { set_error("mdh_build_neighbor_fcna: invalid N, rc or max_neigh"); return MDH_ERR_ARG; }
+    if (N < 0 || N >= 2147483647LL || !(rc > 0) || max_neigh <= 0) { set_error(pattern ? "mdh_build_neighbor_fcna: invalid N, rc or max_neigh" : "mdh_build_neighbor: invalid N, rc or max_neigh"); return MDH_ERR_ARG; }
     DBox b;
     MDH_TRY(make_box(b, box9, origin3, boundary3));
     if (N == 0)
         return MDH_OK;
     Scope sc(stream);
     const double *dx = sc.stage_in(x, (size_t)N, space), *dy = sc.stage_in(y, (size_t)N, space), *dz = sc.stage_in(z, (size_t)N, space);
-    int *dv = sc.stage(verlet, (size_t)(N * max_neigh), space, !fill_pads, true);
-    double *dd = sc.stage(dist, (size_t)(N * max_neigh), space, !fill_pads, true);
-    int *dn = sc.stage(nn, (size_t)N, space, false, true);
-    int *dp = sc.stage(pattern, (size_t)N, space, true, true); // atoms without 12 or 14 neighbours keep the caller's value (cna.cpp:456)
-    // the to-do list of the labels (count first) in a kept block whose two counters — workgroups done (word 0), length (word 64) — are
-    // zero whenever it is idle (the kernel that walks the list clears them when it leaves, cna.hip k_fcna): no memset per call
-    int *done = static_cast<int *>(sc.alloc_kept(sizeof(int) * ((size_t)N + 1 + 64), Scope::KEEP_TODO));
-    int *todo = done ? done + 64 : nullptr;
+    RowsRequest rows;
+    // host space + reference semantics: pads come from the caller's buffers, so they are uploaded too
+    rows.verlet = sc.stage(verlet, (size_t)(N * max_neigh), space, !fill_pads, true);
+    rows.dist = sc.stage(dist, (size_t)(N * max_neigh), space, !fill_pads, true);
+    rows.nn = sc.stage(nn, (size_t)N, space, false, true);
+    rows.M = max_neigh; rows.pads = fill_pads ? RowsRequest::WRITE_PADS : RowsRequest::KEEP_PADS;
+    int *done = nullptr;
+    if (pattern) {
+        rows.pattern = sc.stage(pattern, (size_t)N, space, true, true); // atoms without 12 or 14 neighbours keep the caller's value (cna.cpp:456)
+        // the to-do list of the labels (count first) in a kept block whose two counters — workgroups done (word 0), length (word 64) — are
+        // zero whenever it is idle (the kernel that walks the list clears them when it leaves, cna.hip k_fcna): no memset per call
+        done = static_cast<int *>(sc.alloc_kept(sizeof(int) * ((size_t)N + 1 + 64), Scope::KEEP_TODO));
+        rows.todo = done ? done + 64 : nullptr;
+    }
     const int64_t *dkey = key ? sc.stage_in(key, (size_t)N, space) : nullptr;
     if (sc.failed())
         return sc.error();
@@ -1643,47 +755,15 @@ int mdh_build_neighbor_fcna(const double *x, const double *y, const double *z, i
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
     {
         ProfRange pr("cell_grid", sc.stream());
-        g_next_rows = (int)std::min<int64_t>(max_neigh, 1 << 20);
-        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, dkey, true));
+        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rows_grid(dkey, max_neigh), cg));
     }
-    bool fused = false;
+    RowsDone pass;
     {
         ProfRange pr("k_neighbor", sc.stream());
-        MDH_TRY(neighbor_pass(sc, cg, b, N, rc, dv, dd, dn, max_neigh, fill_pads ? 2 : 1, nullptr, dp, todo, &fused));
+        MDH_TRY(neighbor_pass(sc, cg, b, N, rc, rows, pass));
     }
-    {
-        ProfRange pr("k_fcna", sc.stream());
-        if (fused) launch_fcna_listed(sc.stream(), b, dx, dy, dz, N, dv, max_neigh, dn, dp, rc, todo, done);
-        else launch_fcna_all(sc.stream(), b, dx, dy, dz, N, dv, max_neigh, dn, dp, rc, todo, done);
-        MDH_HIP(hipGetLastError());
-    }
-    sc.keep_confirm(done);
+    if (pattern) MDH_TRY(launch_labels(sc, b, dx, dy, dz, N, rows, rc, done, pass));
     return sc.finish(space);
-}
-
-int mdh_hint_centre_window(int axis, double frac_lo, double frac_hi)
-{
-    g_centre = CellWindow{axis, frac_lo, frac_hi, true};
-    return MDH_OK;
-}
-
-int mdh_hint_cell_window(int axis, double frac_lo, double frac_hi)
-{
-    g_window = CellWindow{axis, frac_lo, frac_hi, true};
-    return MDH_OK;
-}
-
-int mdh_cell_window_check(void *stream)
-{
-    if (!g_window_violations)
-        return MDH_OK;
-    MDH_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
-    if (*(volatile int *)g_window_violations != 0) {
-        *g_window_violations = 0;
-        set_error("the last neighbor build on this thread found atoms outside the cell window it had been promised (mdh_hint_cell_window): its rows are incomplete");
-        return MDH_ERR_ARG;
-    }
-    return MDH_OK;
 }
 
 int mdh_debug_set_neighbor_variant(int v)
@@ -1691,8 +771,6 @@ int mdh_debug_set_neighbor_variant(int v)
     g_neighbor_variant = v;
     return MDH_OK;
 }
-
-int mdh_debug_set_indirect(int on) { return g_indirect.exchange(on ? 1 : 0); }
 
 int mdh_neighbor_count(const double *x, const double *y, const double *z, int64_t N, const double *box9,
                        const double *origin3, const int *boundary3, double rc, int *nn, int *max_count, int space,
@@ -1713,8 +791,11 @@ int mdh_neighbor_count(const double *x, const double *y, const double *z, int64_
     MDH_HIP(hipMemsetAsync(dmax, 0, sizeof(int), sc.stream()));
     CellGrid cg;
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
-    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, nullptr, true));
-    MDH_TRY(neighbor_pass(sc, cg, b, N, rc, nullptr, nullptr, dn, 1, 0, dmax));
+    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rows_grid(nullptr, 0), cg));
+    RowsRequest counts;
+    counts.nn = dn; counts.pads = RowsRequest::COUNT_ONLY; counts.max_count = dmax;
+    RowsDone pass;
+    MDH_TRY(neighbor_pass(sc, cg, b, N, rc, counts, pass));
     MDH_HIP(hipMemcpyAsync(max_count, dmax, sizeof(int), hipMemcpyDeviceToHost, sc.stream()));
     MDH_TRY(sc.finish(space));
     MDH_HIP(hipStreamSynchronize(sc.stream()));
@@ -1757,9 +838,13 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
     int *dn = sc.stage(nn, (size_t)N, space, false, true);
     int *dmax = sc.alloc_n<int>(1);
     const int64_t *dkey = key ? sc.stage_in(key, (size_t)N, space) : nullptr;
-    int *dp = pattern ? sc.stage(pattern, (size_t)N, space, true, true) : nullptr; // atoms without 12 or 14 neighbours keep the caller's value (cna.cpp:456)
+    RowsRequest rows; // the build at a width (pads written); verlet, dist and M are set when the rows exist
+    rows.nn = dn;
+    rows.pattern = pattern ? sc.stage(pattern, (size_t)N, space, true, true) : nullptr; // atoms without 12 or 14 neighbours keep the caller's value (cna.cpp:456)
     int *done = pattern ? static_cast<int *>(sc.alloc_kept(sizeof(int) * ((size_t)N + 1 + 64), Scope::KEEP_TODO)) : nullptr; // (as in mdh_build_neighbor_fcna)
-    int *todo = done ? done + 64 : nullptr;
+    rows.todo = done ? done + 64 : nullptr;
+    RowsRequest counts;
+    counts.nn = dn; counts.pads = RowsRequest::COUNT_ONLY; counts.max_count = dmax;
     if (sc.failed())
         return sc.error();
     hipStream_t st = sc.stream();
@@ -1771,19 +856,10 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
     {
         ProfRange pr("cell_grid", st);
-        g_next_rows = width_hint(N, cg.g.ncell, -1); // the width the last build of this (N, grid) found (0: none yet)
-        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, dkey, true));
+        // (row width: what the last build of this (N, grid) found; 0: none yet)
+        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rows_grid(dkey, width_hint(N, cg.g.ncell, -1)), cg));
     }
-    // the labels of a build: inside the tile kernel where that ran (its leftovers listed in todo), from the finished rows otherwise
-    bool fused = false;
-    auto labels = [&](const int *dv, int64_t M) {
-        if (!dp)
-            return;
-        ProfRange pr("k_fcna", st);
-        if (fused) launch_fcna_listed(st, b, dx, dy, dz, N, dv, M, dn, dp, rc, todo, done);
-        else launch_fcna_all(st, b, dx, dy, dz, N, dv, M, dn, dp, rc, todo, done);
-        sc.keep_confirm(done); // (the list's walker leaves the counters zero)
-    };
+    RowsDone pass;
     // Width hint: the largest count the previous call with the same (N, grid) found.  A sequence of calls on one system (a
     // trajectory, the same analysis repeated) almost always finds the same maximum again, so the rows are built at that
     // width at once and the counts written by the build confirm it — the counting pass is skipped.  A wrong hint costs one
@@ -1791,46 +867,41 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
     int hmax = 0;
     const int hint = space == MDH_DEVICE ? width_hint(N, cg.g.ncell, -1) : 0; // (host buffers: a discarded first allocation would still be a copy-back target)
     bool built = false;
-    if (hint > 0) {
-        if (alloc(user, N, hint, &verlet, &dist) != 0 || !verlet || !dist) { set_error("mdh_build_neighbor_exact: the row allocator failed"); return MDH_ERR_NOMEM; }
-        int *dv = sc.stage(verlet, (size_t)(N * hint), space, false, true);
-        double *dd = sc.stage(dist, (size_t)(N * hint), space, false, true);
+    // rows of width M from the caller's allocator, the build, its labels.  confirm: the largest count goes to hmax behind the build
+    auto build_rows = [&](int64_t M, bool confirm) {
+        if (alloc(user, N, M, &verlet, &dist) != 0 || !verlet || !dist) { set_error("mdh_build_neighbor_exact: the row allocator failed"); return MDH_ERR_NOMEM; }
+        rows.verlet = sc.stage(verlet, (size_t)(N * M), space, false, true);
+        rows.dist = sc.stage(dist, (size_t)(N * M), space, false, true);
+        rows.M = M;
         if (sc.failed())
             return sc.error();
         {
             ProfRange pr("k_neighbor", st);
-            MDH_TRY(neighbor_pass(sc, cg, b, N, rc, dv, dd, dn, hint, 2, nullptr, dp, todo, &fused));
-            hipLaunchKernelGGL(k_max_i32, dim3(1024), dim3(256), 0, st, dn, N, dmax);
-            MDH_HIP(hipMemcpyAsync(&hmax, dmax, sizeof(int), hipMemcpyDeviceToHost, st));
+            MDH_TRY(neighbor_pass(sc, cg, b, N, rc, rows, pass));
+            if (confirm) {
+                hipLaunchKernelGGL(k_max_i32, dim3(1024), dim3(256), 0, st, dn, N, dmax);
+                MDH_HIP(hipMemcpyAsync(&hmax, dmax, sizeof(int), hipMemcpyDeviceToHost, st));
+            }
         }
-        // (enqueued before the width is known: with a confirmed hint — the usual case — the call has no idle gap; after a wrong one the
-        // second build labels again, and a label depends on the atom's neighbours only, not on the width of the rows: an atom the
-        // wasted pass labelled had its 12 or 14 neighbours listed in full, anything else it left to the list)
-        labels(dv, hint);
+        return pattern ? launch_labels(sc, b, dx, dy, dz, N, rows, rc, done, pass) : MDH_OK;
+    };
+    if (hint > 0) {
+        // (the labels are enqueued before the width is known: with a confirmed hint — the usual case — the call has no idle gap; after a
+        // wrong one the second build labels again, and a label depends on the atom's neighbours only, not on the width of the rows: an
+        // atom the wasted pass labelled had its 12 or 14 neighbours listed in full, anything else it left to the list)
+        MDH_TRY(build_rows(hint, /*confirm=*/true));
         MDH_HIP(hipStreamSynchronize(st));
         built = (hmax > 1 ? hmax : 1) == hint;
     } else {
         ProfRange pr("k_neighbor_count", st);
-        MDH_TRY(neighbor_pass(sc, cg, b, N, rc, nullptr, nullptr, dn, 1, 0, dmax));
+        MDH_TRY(neighbor_pass(sc, cg, b, N, rc, counts, pass));
         MDH_HIP(hipMemcpyAsync(&hmax, dmax, sizeof(int), hipMemcpyDeviceToHost, st));
         MDH_HIP(hipStreamSynchronize(st));
     }
     const int64_t M = hmax > 1 ? hmax : 1;
     *width = M;
     width_hint(N, cg.g.ncell, (int)(M <= 4096 ? M : 0));
-    if (!built) {
-        if (alloc(user, N, M, &verlet, &dist) != 0 || !verlet || !dist) { set_error("mdh_build_neighbor_exact: the row allocator failed"); return MDH_ERR_NOMEM; }
-        int *dv = sc.stage(verlet, (size_t)(N * M), space, false, true);
-        double *dd = sc.stage(dist, (size_t)(N * M), space, false, true);
-        if (sc.failed())
-            return sc.error();
-        {
-            ProfRange pr("k_neighbor", st);
-            fused = false;
-            MDH_TRY(neighbor_pass(sc, cg, b, N, rc, dv, dd, dn, M, 2, nullptr, dp, todo, &fused));
-        }
-        labels(dv, M);
-    }
+    if (!built) MDH_TRY(build_rows(M, /*confirm=*/false));
     MDH_HIP(hipGetLastError());
     return sc.finish(space);
 }
@@ -1851,7 +922,8 @@ int mdh_filter_overlap_atom(const double *x, const double *y, const double *z, i
         return sc.error();
     CellGrid cg;
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
-    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, false, cg));
+    GridRequest rq; rq.wrap_first = true; // sorted coordinate arrays, cells in any order
+    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rq, cg));
     if (b.tri)
         hipLaunchKernelGGL(k_filter_overlap<true>, dim3(grid_for(N, 256)), dim3(256), 0, sc.stream(), cg.xs, cg.ys, cg.zs, cg.order, cg.cell_start, N, b, cg.g, rc, dk);
     else
@@ -1874,10 +946,6 @@ int mdh_sort_verlet_by_distance(int *verlet, double *dist, int64_t N, int64_t M,
         return sc.finish(space);
     if (M > SORT_LDS_WIDEST) { // (the reference's selection sort, neighbor.cpp: its order among EQUAL distances — a perfect lattice — is part of the result)
         hipLaunchKernelGGL(k_sort_rows_wide, dim3(grid_for(N, 256)), dim3(256), 0, sc.stream(), dv, dd, N, M, k);
-        return sc.finish(space);
-    }
-    if (g_neighbor_variant == 3 && (size_t)M * SORT_ROWS * 12 <= 60 * 1024) {
-        hipLaunchKernelGGL(k_sort_rows_r2, dim3(grid_for(N, SORT_ROWS)), dim3(SORT_ROWS), (size_t)M * SORT_ROWS * 12, sc.stream(), dv, dd, N, M, k);
         return sc.finish(space);
     }
     int L = 1; // lanes to a row: the fewest that keep the rows of a wave within ~10 KB of LDS
@@ -1956,18 +1024,3 @@ int mdh_average_by_neighbor(double rc, const int *verlet, const double *dist, co
 
 MDH_WARM_UNIT(neighbor)
 
-// the grouping rule of k_assign on the host (assign_groups.hpp), slice by slice
-extern "C" int64_t mdh_debug_assign_groups(const int *cells, int64_t n, int *head, int *count, int *rank)
-{
-    int64_t atomics = 0;
-    for (int64_t s0 = 0; s0 < n; s0 += 64) {
-        int c[64], h[64], k[64], r[64];
-        for (int l = 0; l < 64; ++l) c[l] = s0 + l < n ? cells[s0 + l] : -1 - l;
-        mdh::assign_groups::slice(c, h, k, r);
-        for (int l = 0; l < 64 && s0 + l < n; ++l) {
-            head[s0 + l] = h[l]; count[s0 + l] = k[l]; rank[s0 + l] = r[l];
-            atomics += k[l] > 0 && c[l] >= 0 ? 1 : 0;
-        }
-    }
-    return atomics;
-}

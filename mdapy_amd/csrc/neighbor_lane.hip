@@ -993,7 +993,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                 for (int d = 32; d >= 1; d >>= 1) maxk = max(maxk, __shfl_xor(maxk, d, 64));
                 const uint64_t row = (uint64_t)(unsigned)id * (unsigned)M;
                 const int gend = write_pads ? M : min(M, maxk);
-                const bool ids_only = (write_pads & 2) != 0; // (uniform) lane_ids_only: no distance is computed or stored
+                const bool ids_only = (write_pads & 2) != 0; // (uniform) RowsRequest::ids_only: no distance is computed or stored
                 for (int g0 = 0; g0 < gend; g0 += 4) {
                     int idv[4];
                     double dv[4];
@@ -1375,18 +1375,14 @@ static LanePlan plan_lane_fresh(const DBox &b, const Grid &g, int64_t N, int64_t
     return p;
 }
 
-// count == true: nn and *max_count only (first pass of the exact-width variant); M is then 1
-// The next build's wide instance writes ids and counts only (knn.hip: the rows of a cutoff build as candidates of a k-nearest search;
-// the distances would be 8 M bytes per atom written and ~300 instructions per four slots computed for nobody).  The other kernels of
-// a build (rows of <= 16 slots, the mop-up code) write distances as always: the caller still passes a buffer.
-static thread_local bool g_lane_ids_only = false;
-void lane_ids_only(bool on) { g_lane_ids_only = on; }
-
+// rows (RowsRequest, grid.hpp).  COUNT_ONLY: nn and *max_count only; M is then 1
 int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, int64_t N, const DBox &b, double rc,
-                         int *verlet, double *dist, int *nn, int64_t M, bool fill_pads, bool count, int *max_count,
-                         TileFilter &tf, int *pattern)
+                         const RowsRequest &rows, TileFilter &tf)
 {
     using namespace lane;
+    const bool count = rows.pads == RowsRequest::COUNT_ONLY, fill_pads = rows.pads == RowsRequest::WRITE_PADS;
+    int *const verlet = rows.verlet, *const nn = rows.nn, *const max_count = rows.max_count, *const pattern = count ? nullptr : rows.pattern;
+    double *const dist = rows.dist; const int64_t M = count ? 1 : rows.M;
     int nt[3];
     for (int d = 0; d < 3; ++d) {
         const int T = d == 2 ? plan.tz : plan.txy;
@@ -1430,7 +1426,7 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
     const dim3 grid((unsigned)(per * 8));
     const size_t lds = lds_bytes(plan.cap, count ? 1 : M, plan.tk8, plan.rw, pattern != nullptr);
     const int cen_lo = cg.cen_hi > cg.cen_lo ? cg.cen_lo : 0, cen_hi = cg.cen_hi > cg.cen_lo ? cg.cen_hi : 0x7fffffff;
-    const int Mi = (int)M, wp = fill_pads ? (g_lane_ids_only ? 3 : 1) : 0; // bit 1: the wide instance neither computes nor stores the distances (lane_ids_only)
+    const int Mi = (int)M, wp = fill_pads ? (rows.ids_only ? 3 : 1) : 0; // bit 1: the wide instance neither computes nor stores the distances (RowsRequest::ids_only)
     const float negc = -plan.mid;
     const int nt2b = nt[2] * nsub;
     // second pass: workgroups walk the listed tiles' slices.  Nothing was listed by the previous build with this (N, grid)

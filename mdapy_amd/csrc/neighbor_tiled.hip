@@ -547,8 +547,9 @@ static void launch_one(hipStream_t st, const CellGrid &cg, const DBox &b, double
 }
 
 int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, int64_t N, const DBox &b, double rc,
-                          int *verlet, double *dist, int *nn, int64_t M, bool fill_pads, TileFilter &tf)
+                          const RowsRequest &rows, TileFilter &tf)
 {
+    const bool fill_pads = rows.pads == RowsRequest::WRITE_PADS;
     const TileShape ts{plan.tile, plan.tile_z};
     int nt[3];
     for (int d = 0; d < 3; ++d) {
@@ -578,8 +579,8 @@ int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, 
     }
     // Two launches, one of which returns at once on the device flag: image numbers from the cell / atom codes when
     // the binning pass found them valid (and the grid allows it), the exact threshold search otherwise.
-    if (plan.cellshift) launch_one<true>(st, cg, b, rc, verlet, dist, nn, (int)M, fill_pads, tile_flag, nt, 0, ts, tile_list, slot + ntiles, est_live, false);
-    launch_one<false>(st, cg, b, rc, verlet, dist, nn, (int)M, fill_pads, tile_flag, nt, plan.cellshift ? 1 : -1, ts, tile_list, slot + ntiles, est_live, plan.cellshift);
+    if (plan.cellshift) launch_one<true>(st, cg, b, rc, rows.verlet, rows.dist, rows.nn, (int)rows.M, fill_pads, tile_flag, nt, 0, ts, tile_list, slot + ntiles, est_live, false);
+    launch_one<false>(st, cg, b, rc, rows.verlet, rows.dist, rows.nn, (int)rows.M, fill_pads, tile_flag, nt, plan.cellshift ? 1 : -1, ts, tile_list, slot + ntiles, est_live, plan.cellshift);
     MDH_HIP(hipGetLastError());
     tf.flag = tile_flag;
     tf.any = cg.flags + 2;

@@ -214,7 +214,10 @@ int mdh_spatial_sort(const double *x, const double *y, const double *z, int64_t 
             break;
         edge *= 1.26;
     }
-    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, true, cg, nullptr, true, true)); // (scattered input: that is why the caller sorts)
+    GridRequest rq;
+    rq.wrap_first = rq.sort_desc = true;
+    rq.atoms = GridRequest::FOR_ROWS_UNORDERED; // (that is why the caller sorts)
+    MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rq, cg));
     hipLaunchKernelGGL(k_unpack_sorted, dim3(grid_for(N, 256)), dim3(256), 0, st, cg.pk, N, oxs, oys, ozs, operm);
     int binned = 0;
     MDH_HIP(hipMemcpyAsync(&binned, cg.cell_start + cg.g.ncell, sizeof(int), hipMemcpyDeviceToHost, st));

@@ -512,7 +512,8 @@ int mdh_rdf_streaming(const double *x, const double *y, const double *z, const i
         cg.g.ncell = (int64_t)cg.g.nc[0] * cg.g.nc[1] * cg.g.nc[2];
         cg.g.rc_inv = 1.0 / rc;
         cg.g.mode = 1;
-        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, true, false, cg));
+        GridRequest rq; rq.wrap_first = true; // sorted coordinate arrays, cells in any order
+        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rq, cg));
         const size_t tile_lds = (((size_t)hsize * 4 + 15) & ~(size_t)15) + 4 * sizeof(RdfWave);
         // the frame of 3x3x3 cells along the worst Cartesian axis, in units of the orthogonal kernel's 2.7 rc
         double tol_scale = 1.0;

@@ -375,6 +375,7 @@ int make_box(DBox &b, const double *box9, const double *origin3, const int *boun
 
 namespace mdh {
 void warm_prof(hipStream_t st);
+void warm_cell_grid(hipStream_t st);
 void warm_neighbor(hipStream_t st);
 void warm_neighbor_tiled(hipStream_t st);
 void warm_neighbor_lane(hipStream_t st);
@@ -495,6 +496,7 @@ int mdh_warm(void)
     hipLaunchKernelGGL(mdh::k_warm_runtime, dim3(1), dim3(64), 0, nullptr);
     hipLaunchKernelGGL(mdh::k_warm_scratch, dim3(1), dim3(64), 0, nullptr, 0, static_cast<int *>(nullptr));
     mdh::warm_prof(nullptr);
+    mdh::warm_cell_grid(nullptr);
     mdh::warm_neighbor(nullptr);
     mdh::warm_neighbor_tiled(nullptr);
     mdh::warm_neighbor_lane(nullptr);

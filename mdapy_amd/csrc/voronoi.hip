@@ -418,7 +418,8 @@ static int voronoi_solve(void *stream, const double *dx, const double *dy, const
                     return MDH_ERR_ARG;
                 }
                 Scope inner(stream);
-                MDH_TRY(build_cell_grid(inner, dx, dy, dz, N, b, true, true, cg));
+                GridRequest rq; rq.wrap_first = rq.sort_desc = true; // sorted coordinate arrays, cells in reference order
+                MDH_TRY(build_cell_grid(inner, dx, dy, dz, N, b, rq, cg));
                 int *cnts = inner.alloc_n<int>((size_t)nl);
                 int *dmax = inner.alloc_n<int>(1);
                 if (inner.failed())

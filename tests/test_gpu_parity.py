@@ -1290,6 +1290,15 @@ def test_system_flow_perfect_crystals_and_errors():
 
 
 # ------------------------------------------------------------------ PTM (a13): HIP kernel vs oracle/_ref, the reference's own library
+def _window_slab():
+    """a slab of a rattled fcc crystal, fractions [0.30, 0.52) of x -> (positions, box, box length along x)"""
+    pos, box = lattice_positions("fcc", 3.615, 40, 6, 6)
+    pos = pos + np.random.default_rng(8).normal(0, 0.05, pos.shape)
+    L = box[0][0] if np.ndim(box) == 2 else box[0]
+    f = (pos[:, 0] / L) % 1.0
+    return pos[(f >= 0.30) & (f < 0.52)], box, L
+
+
 def test_neighbor_cell_window_hint_same_rows_and_broken_promise_is_reported():
     """mdh_hint_cell_window (a rank's slab of a decomposed system): the build's passes over the cells of the global grid and
     the tile kernel's range cover the promised planes only — rows, counts, distances bit-identical to the build without the
@@ -1297,11 +1306,7 @@ def test_neighbor_cell_window_hint_same_rows_and_broken_promise_is_reported():
     NEXT build of the thread refuses loudly."""
     import torch
 
-    pos, box = lattice_positions("fcc", 3.615, 40, 6, 6)
-    pos = pos + np.random.default_rng(8).normal(0, 0.05, pos.shape)
-    L = box[0][0] if np.ndim(box) == 2 else box[0]
-    f = (pos[:, 0] / L) % 1.0
-    pos = pos[(f >= 0.30) & (f < 0.52)]
+    pos, box, L = _window_slab()
     N = len(pos)
     rc, M = 0.854 * 3.615, 18
     dev = torch.device("cuda", 0)
@@ -1347,6 +1352,38 @@ def test_neighbor_cell_window_hint_same_rows_and_broken_promise_is_reported():
     assert deep.sum() > 100 and np.array_equal(nw[deep], ref_n[deep])
     assert np.array_equal(vw[deep][:, :M], ref_v[deep]) and (vw[deep][:, M:] == -1).all()
     assert ((vw >= -1) | (vw == -7)).all() and (vw < N).all() and ((nw == -7) | ((nw >= 0) & (nw <= Mw))).all()
+
+
+def test_window_hints_are_spent_on_a_grid_build_that_makes_no_rows():
+    """The hints belong to the NEXT grid build of the thread, whatever it is for: a cell window and a centre window that would both
+    lose rows, then filter_overlap_atom (a grid of sorted coordinate arrays: nothing there knows what a window leaves undone), then a
+    build without a hint — rows, distances and counts bit-equal to a build made before any hint, no broken promise on record."""
+    import torch
+
+    pos, box, _ = _window_slab()
+    N = len(pos)
+    rc, M = 0.854 * 3.615, 18
+    dev = torch.device("cuda", 0)
+    x, y, z = (torch.from_numpy(np.ascontiguousarray(pos[:, k])).to(dev) for k in range(3))
+
+    def build():
+        v = torch.empty((N, M), dtype=torch.int32, device=dev)
+        d = torch.empty((N, M), dtype=torch.float64, device=dev)
+        n = torch.empty((N,), dtype=torch.int32, device=dev)
+        _neighbor.build_neighbor(x, y, z, box, ORG0, PBC, rc, v, d, n, 1, fill_pads=True)
+        torch.cuda.synchronize()
+        return v.cpu().numpy(), d.cpu().numpy(), n.cpu().numpy()
+
+    ref = build()
+    assert ref[2].max() >= 12
+    _neighbor.hint_cell_window(0, 0.40, 0.54)    # (a third of the atoms lie below it)
+    _neighbor.hint_centre_window(0, 0.44, 0.50)  # (rows for a quarter of the atoms only)
+    keep = _neighbor.filter_overlap_atom(x, y, z, box, ORG0, PBC, rc)
+    assert len(keep) == N and keep[0]
+    got = build()
+    assert all(np.array_equal(a, b_) for a, b_ in zip(got, ref))
+    build()  # (raises nothing)
+    _neighbor.cell_window_check()
 
 
 from _ptm_cases import compare_ptm, ptm_cases

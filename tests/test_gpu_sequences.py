@@ -387,6 +387,41 @@ def test_signature_table_of_the_rows_path_never_changes_a_result(monkeypatch):
                 search(small)
 
 
+def test_ids_only_rows_of_a_search_do_not_reach_the_next_build(monkeypatch):
+    """A k-nearest search on the rows path asks its cutoff build for ids only (32-slot rows on the tile kernel's wide instance, which
+    then neither computes nor stores a distance).  That belongs to the search's own build: build_neighbor(rc = 4.3, 32 slots,
+    fill_pads) on the same thread right behind it — the same instance, asserted through mdh_debug_neighbor_plan — writes ids,
+    distances and counts bit-equal to the oracle's, and so it does in front of the search; the search equals the oracle both times."""
+    from mdapy_amd import _fast_knn, _lib, _neighbor
+    from oracle import oracle as O
+
+    monkeypatch.setenv("MDH_KNN_ROWS_MIN", "1000")
+    f = T.start("fcc", (12, 12, 12), seed=71, rattle=0.05, shuffle=False)
+    assert f.n == 6912
+    k, rc, M = 18, 4.3, 32  # (the search's own radius is ~4.3 A here: the box spans >= 7.5 radii, >= 7 cells per axis)
+    want_v, want_d, want_n = np.full((f.n, M), -1, np.int32), np.full((f.n, M), rc + 1.0), np.zeros(f.n, np.int32)
+    O.build_neighbor(*f.where(), rc, want_v, want_d, want_n, 8)
+    assert 12 < want_n.max() <= M
+    want_knn = T.expected_knn(f, k)
+    plan = np.zeros(8, np.int32)
+
+    def search():
+        idx, dist = np.zeros((f.n, k), np.int32), np.zeros((f.n, k))
+        assert _report(lambda: _fast_knn.knn(*f.where(), k, idx, dist, 1)) == (1, 1)  # (rows built, searched from the rows)
+        assert np.array_equal(idx, want_knn["rows"]) and np.array_equal(dist, want_knn["dist"])
+
+    def build():
+        v, d, n = np.empty((f.n, M), np.int32), np.full((f.n, M), np.nan), np.empty(f.n, np.int32)
+        _lib.lib().mdh_debug_neighbor_plan(plan.ctypes.data)  # ([7] = 0 from here on: the plan read below is this build's)
+        _neighbor.build_neighbor(*f.where(), rc, v, d, n, 1, fill_pads=True)
+        _lib.lib().mdh_debug_neighbor_plan(plan.ctypes.data)
+        assert plan[7] == 1 and plan[0] > 0 and not plan[4] & 2, plan.tolist()  # the tile kernel took it, wide instance
+        assert np.array_equal(v, want_v) and np.array_equal(d, want_d) and np.array_equal(n, want_n)
+
+    search(); build()
+    build(); search()
+
+
 # ================================================================================================================================
 # B4  atoms the rows build does not bin
 # ================================================================================================================================
