@@ -437,6 +437,16 @@ int mdh_atomic_strain(const int *verlet, const int *nn, int64_t N, int64_t M, co
                       const double *ref_z, const double *cur_x, const double *cur_y, const double *cur_z, const double *map9_host,
                       double *shear, double *volumetric, int space, void *stream);
 
+/* ---- _chill_plus ------------------------------------------------------ */
+/* replaces _chill_plus.compute_chill_plus                   src/chill_plus.cpp:76-179
+ * CHILL+ (Nguyen & Molinero 2015) over a cutoff list: an entry jj < nn[i] is a bond iff dist[i, jj] <= rc and verlet[i, jj] >= 0.
+ * pattern (N) i32: 0 other, 1 hexagonal ice, 2 cubic ice, 3 interfacial ice, 4 hydrate, 5 interfacial hydrate.  f32 arithmetic
+ * in the reference's order; e^{i phi} is (dx, dy) / |(dx, dy)| instead of expf(i atan2f(dy, dx)), so a label may differ from the
+ * reference's where a bond's c_ij sits on one of the three thresholds to within single-precision noise. */
+int mdh_chill_plus(const double *x, const double *y, const double *z, int64_t N, const double *box9_host,
+                   const double *origin3_host, const int *boundary3_host, const int *verlet, const double *dist, const int *nn,
+                   int64_t M, double rc, int *pattern, int space, void *stream);
+
 /* ---- _wcp ------------------------------------------------------------- */
 /* replaces _wcp.get_wcp                                    src/warren_cowley_parameter.cpp:9-80; wcp (ntype,ntype) */
 int mdh_wcp(const int *verlet, const int *nn, const int *type, int64_t N, int64_t M, int ntype, double *wcp,

@@ -16,6 +16,7 @@ from .polyhedral_template_matching import PolyhedralTemplateMatching
 from .radial_distribution_function import RadialDistributionFunction
 from .warren_cowley_parameter import WarrenCowleyParameter
 from .atomic_strain import AtomicStrain
+from .chill_plus import ChillPlus
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -23,6 +24,6 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain",
+    "AtomicStrain", "ChillPlus",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

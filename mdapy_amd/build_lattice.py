@@ -1,6 +1,6 @@
 """Crystal builder for the benchmark and test inputs of the hot path — the standard-orientation subset of
-``mdapy.build_crystal`` (src/mdapy/build_lattice.py:657-907): sc, fcc, bcc, diamond in the cubic cell, hcp and a graphene
-layer in the hexagonal cell.  Atoms come cell by cell, (ix, iy, iz)-lexicographic with the basis innermost, at
+``mdapy.build_crystal`` (src/mdapy/build_lattice.py:657-907): sc, fcc, bcc, diamond in the cubic cell, hcp, lonsdaleite and a
+graphene layer in the hexagonal cell.  Atoms come cell by cell, (ix, iy, iz)-lexicographic with the basis innermost, at
 ``basis @ cell + ((ix a1 + iy a2) + iz a3)`` — the very expression the reference's replication kernel evaluates
 (src/repeat_cell.cpp:41-59), so knife-edge cutoffs see identical coordinates.  Miller-index orientations and ordered
 multi-species structures are outside the hot path."""
@@ -20,7 +20,12 @@ _BASIS = {
     # fcc + the same lattice shifted by a quarter of the body diagonal (written out: the order of the sites is part of the output)
     "diamond": _FCC_SITES + [[0.25, 0.25, 0.25], [0.75, 0.75, 0.25], [0.75, 0.25, 0.75], [0.25, 0.75, 0.75]],
 }
-_HEX_BASIS = {"hcp": [[0.0, 0.0, 0.0], [1.0 / 3.0, 2.0 / 3.0, 0.5]], "graphene": [[0.0, 0.0, 0.0], [1.0 / 3.0, 2.0 / 3.0, 0.0]]}
+_HEX_BASIS = {
+    "hcp": [[0.0, 0.0, 0.0], [1.0 / 3.0, 2.0 / 3.0, 0.5]],
+    "graphene": [[0.0, 0.0, 0.0], [1.0 / 3.0, 2.0 / 3.0, 0.0]],
+    # hexagonal diamond (the oxygen sites of ice Ih): the hcp sites and each one's partner 3/8 c above it
+    "lonsdaleite": [[1.0 / 3.0, 2.0 / 3.0, 0.0], [2.0 / 3.0, 1.0 / 3.0, 0.5], [1.0 / 3.0, 2.0 / 3.0, 0.375], [2.0 / 3.0, 1.0 / 3.0, 0.875]],
+}
 
 
 def unit_cell(structure, a, c=None):
@@ -32,10 +37,10 @@ def unit_cell(structure, a, c=None):
         if c is None:
             if kind == "graphene":
                 raise ValueError("graphene needs c (the spacing of the periodic images along z)")
-            c = a * float(np.sqrt(8 / 3))  # ideal close packing
+            c = a * float(np.sqrt(8 / 3))  # ideal close packing (lonsdaleite: ideal tetrahedra)
         hexagonal = np.array([[a, 0.0, 0.0], [-0.5 * a, 0.5 * np.sqrt(3.0) * a, 0.0], [0.0, 0.0, c]])
         return hexagonal, np.array(_HEX_BASIS[kind])
-    raise ValueError(f"Unrecognized structure '{structure}'. Supported here: {sorted(_BASIS) + ['hcp', 'graphene']}")
+    raise ValueError(f"Unrecognized structure '{structure}'. Supported here: {sorted(_BASIS) + sorted(_HEX_BASIS)}")
 
 
 def _supercell(cell, nx, ny, nz):

@@ -9,6 +9,8 @@ from . import _atomtemp as atomtemp
 # (not in NAMES: the CPU suite's oracle backend asserts an adapter for every name there, and the oracle has no bond analysis;
 # its tests install a restatement of their own as kernels.bond_analysis)
 from . import _bond_analysis as bond_analysis
+# (not in NAMES either: the oracle has no CHILL+; its tests install a restatement as kernels.chill_plus)
+from . import _chill_plus as chill_plus
 from . import _cluster as cluster
 from . import _cna as cna
 from . import _cnp as cnp

@@ -23,6 +23,7 @@ from .atomic_temperature import AtomicTemperature
 from .bond_analysis import BondAnalysis
 from .box import Box
 from .centro_symmetry_parameter import CentroSymmetryParameter
+from .chill_plus import ChillPlus
 from .cluster_analysis import ClusterAnalysis
 from .common_neighbor_analysis import CommonNeighborAnalysis
 from .common_neighbor_parameter import CommonNeighborParameter
@@ -89,6 +90,7 @@ _ARGS = {
     "cal_common_neighbor_parameter": ("rc", "max_neigh"),
     "cal_structure_entropy": ("rc", "sigma", "use_local_density", "average_rc", "max_neigh"),
     "cal_atomic_temperature": ("rc", "factor", "max_neigh"),
+    "cal_chill_plus": ("cutoff",),
     "cal_steinhardt_bond_orientation": ("llist", "use_voronoi", "nnn", "rc", "average", "use_weight", "weight", "wl", "wlhat",
                                         "a_face_area_threshold", "r_face_area_threshold", "identify_liquid"),
     "cal_radial_distribution_function": ("rc", "nbin", "max_neigh", "streaming"),
@@ -313,7 +315,7 @@ class System:
         if mine is None and "verlet_list" in twin.__dict__:
             twin._forget(_LIST)
         bound = dict(zip(_ARGS.get(name, ()), args), **kwargs)
-        reach = bound.get("rc", bound.get("average_rc"))
+        reach = bound.get("rc", bound.get("cutoff", bound.get("average_rc")))
         if name == "cal_angular_distribution_function":
             reach = _adf_reach(bound.get("rc_dict"))
         if name in ("cal_bond_analysis", "cal_angular_distribution_function") and isinstance(reach, (int, float, np.integer, np.floating)) \
@@ -720,6 +722,16 @@ class System:
         job = AtomicTemperature(self._get_compute_view()[1], self.verlet_list, self.distance_list, rc, factor)
         job.compute()
         self._store(atomic_temp=job.T)
+
+    @_on_twin
+    def cal_chill_plus(self, cutoff=3.5):
+        """column ``chill_plus``: 0 other, 1 hexagonal ice, 2 cubic ice, 3 interfacial ice, 4 gas hydrate, 5 interfacial gas
+        hydrate (CHILL+); the system holds the molecule centres only (oxygens or water beads, no hydrogens)"""
+        self._require_cutoff_list(cutoff, None)
+        cell, frame = self._get_compute_view()
+        job = ChillPlus(frame, cell, cutoff, self.verlet_list, self.distance_list, self.neighbor_number)
+        job.compute()
+        self._store(chill_plus=job.pattern)
 
     def cal_cluster_analysis(self, rc=5.0, max_neigh=None):
         """column ``cluster_id`` and attribute ``cluster_number``; ``rc`` one number or a dict per type pair"""
