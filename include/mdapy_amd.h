@@ -94,9 +94,19 @@ int mdh_debug_set_neighbor_variant(int variant);
  * some spatial order keeps no cell-sorted copy of the atoms, its kernels read them through the cell-sorted id list;
  * 0 = the cell-sorted 32-byte records always (what unordered input gets either way).  Returns the previous value.  Results are identical. */
 int mdh_debug_set_indirect(int on);
+/* A/B switch for measurements and tests: 1 (default; MDH_SLOT_GRID in the environment) = a neighbor build of spatially ordered
+ * input whose cells held at most eight atoms last time bins the atoms straight into fixed cell slots (no prefix sum, no second
+ * scatter); 0 = the compact cell order always; 2 = 1, and the history of every (N, grid) forgotten (the next
+ * build of each is a first one: compact).  Returns the previous value.  Results are identical.
+ * mdh_debug_slot_grid_counters(out4), after the caller synchronised the stream: {1 if the last neighbor build's grid was a slot
+ * grid, 1 if the last build of that signature saw a cell of more than out4[3] atoms, the atoms of such a cell (those above
+ * out4[3] went to the spill list), atoms a cell holds in place}.  mdh_debug_slot_grid_rule: the taking rule on the host (1 = slot grid). */
+int mdh_debug_set_slot_grid(int on);
+int mdh_debug_slot_grid_counters(int64_t *out4);
+int mdh_debug_slot_grid_rule(int ordered, int keyed, int windowed, int row_width, int64_t ncell, int64_t N, int seen, int big, int listed);
 /* test hook: the tile plan of the last neighbor build that took the LDS-tile kernel (neighbor_lane.hip):
  * plan8 = {tile cells in x/y, in z, halo atoms per tile, LDS bytes, box full of atoms, 1000 * atoms per cell,
- * cells of the occupied region, 1 if a plan was made since the last query}. */
+ * cells of the occupied region, 1 if a plan was made since the last query}; bit 8 of plan8[4]: the build's cell grid was a slot grid. */
 int mdh_debug_neighbor_plan(int *plan8);
 /* test hook: fixed-cutoff CNA (mdh_fcna, src/cna.cpp:429-506): 0 = single-precision pair tests with a decision band where the
  * box allows (default; atoms inside the band are finished with the reference's double-precision expression), 1 = the

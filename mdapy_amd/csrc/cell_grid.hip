@@ -10,11 +10,17 @@
 //                  linked list is walked),
 //   xs,ys,zs f64[N] (raw positions gathered into cell order, so a cell's atoms — and the 3 cells of a z-run — are
 //                  contiguous and loads are coalesced).
+// The slot grid (CellGrid::slot_cap, grid.hpp; neighbor builds of spatially ordered input whose cells were small last time):
+//   count u32[ncell] (two arrays in one kept block, alternating from one slot build to the next), slots i32[2][ncell][4] (the ids
+//   of a cell where its counter placed them, then sorted in place: k_assign<SLOT> -> k_sort_slots, no scan, no scatter),
+//   spill int2[N] + a counter (the atoms of cells that hold more than SLOT_CAP).
 #include "common.hpp"
 #include "grid.hpp"
 #include "assign_groups.hpp"
 #include <algorithm>
 #include <atomic>
+#include <mutex>
+#include <vector>
 
 namespace mdh {
 // 1: neighbor builds of input in spatial order keep no sorted copy of the atoms (CellGrid::ix); 0: the 32-byte records always
@@ -31,13 +37,18 @@ struct CellPlanes { int p0, p1, p2, p3; int *bad; }; // planes [p0, p1) and [p2,
 // One atomic per group of lanes of a cell up to three lanes apart (assign_groups.hpp) and ONE 8-byte store of (cell, slot) per atom:
 // 133.8 -> 90-104 us at 10 M lattice atoms (8.23 M -> 6.73 M atomics, the distinct cells per slice; with runs of adjacent lanes and
 // two 4-byte stores before), profiles/assign_window.md.
-template <bool TRI, int K>
+// SLOT (a slot grid, CellGrid::slot_cap): the slot the counter hands out IS the atom's final place — its id goes to
+// slots[cell * SLOT_CAP + slot], a scattered 4-byte store in place of the coalesced 8-byte entry, and the scan and the scatter that
+// turned the entries into a cell order are not run at all (slots in two planes of four per cell, slot_pos; slot_hi: the second);
+// an atom whose cell is full goes to the spill list as (cell, id), the count keeps running so that every reader sees the overflow
+template <bool TRI, int K, bool SLOT = false>
 __global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, const double *__restrict__ y,
                                                 const double *__restrict__ z, int64_t N, DBox b, Grid g,
                                                 int wrap_first, int2 *__restrict__ ent,
                                                 unsigned *__restrict__ cell_count, unsigned *__restrict__ ctl, unsigned gen,
                                                 double slack, unsigned short *__restrict__ mv, CellPlanes win,
-                                                CellGrid::Packed *__restrict__ rec, int drop_absent)
+                                                CellGrid::Packed *__restrict__ rec, int drop_absent, int *__restrict__ slots = nullptr,
+                                                int2 *__restrict__ spill = nullptr, unsigned *__restrict__ spill_n = nullptr, int64_t slot_hi = 0)
 {
     const int lane = threadIdx.x & 63;
     const int64_t i0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * (64 * K) + lane;
@@ -131,6 +142,14 @@ __global__ __launch_bounds__(256) void k_assign(const double *__restrict__ x, co
     for (int k = 0; k < K; ++k) {
         const unsigned bs = __shfl(base[k], head[k], 64);
         const int64_t i = i0 + 64 * k;
+        if (SLOT) {
+            if (i < N && cells[k] >= 0) {
+                const unsigned s = bs + (unsigned)slot[k];
+                if (s < (unsigned)SLOT_CAP) slots[slot_pos(cells[k], (int)s, slot_hi)] = (int)i;
+                else spill[atomicAdd(spill_n, 1u)] = make_int2(cells[k], (int)i); // (at most one entry per atom: the list holds N)
+            }
+            continue;
+        }
         if (i < N) // (cell < 0: absent, or outside a promised window — k_scatter leaves the atom out)
             ent[i] = make_int2(cells[k], (int)(bs + (unsigned)slot[k]));
     }
@@ -399,14 +418,28 @@ __device__ __forceinline__ void sort_cell_net(int *__restrict__ order, int s, in
 // more than eight atoms without a key: the ids are copied there and every atom is PLACED at the number of larger ids of its
 // cell — n^2 independent, cached reads instead of the insertion sort's chain of dependent ones (dense cells, rc = 5 A: 11 atoms
 // per cell, up to 50 in the fat last cells: 239 -> 204 us at 10 M atoms, 131 -> 94 us at 3.4 M)
+// A cell of more than SLOT_CAP atoms, seen by the in-cell sort of a build whose signature may take the slot grid next time: the
+// build's generation is stamped into ctl[3] (once per build or nearly: the others find the stamp in L2 and leave) and the cell's
+// count goes to the signature's pinned words (SlotHistory::host[1]).  The last kernel of the pass over the grid publishes the
+// stamp as host[0] = 1 or 0 (CellGrid::big_sink).
+__device__ __forceinline__ void report_big_cell(unsigned *__restrict__ ctl, unsigned gen, int *__restrict__ sink, int n)
+{
+    if (__hip_atomic_load(&ctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen)
+        return;
+    __hip_atomic_store(&ctl[3], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sink[1] = n;
+}
+
 __global__ __launch_bounds__(256) void k_sort_cells(const int *__restrict__ cell_start, int *__restrict__ order,
-                                                    int64_t ncell, const int64_t *__restrict__ key, int *__restrict__ tmp)
+                                                    int64_t ncell, const int64_t *__restrict__ key, int *__restrict__ tmp,
+                                                    unsigned *__restrict__ ctl = nullptr, unsigned gen = 0, int *__restrict__ big_sink = nullptr)
 {
     int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ncell)
         return;
     const int s = cell_start[c], e = cell_start[c + 1];
     const int n = e - s;
+    if (big_sink && n > SLOT_CAP) report_big_cell(ctl, gen, big_sink, n);
     if (n <= 1)
         return;
     if (n <= 4) {
@@ -480,6 +513,51 @@ __global__ __launch_bounds__(256) void k_sort_cells_dense(const int *__restrict_
             order[s + larger] = mine;
         }
     }
+}
+
+// The in-cell sort of a slot grid, one thread per cell: the cell's ids as one or two 16-byte loads (one per plane), the networks above in
+// registers (descending; the slots behind the count sink to the end and are stored back as they fall, nobody reads them), one or
+// two 16-byte stores.  A cell whose count ran past SLOT_CAP sorts its first SLOT_CAP ids; the walkers merge the spill list in
+// (neighbor.hip), and the build is reported (report_big_cell) so that the next one of this signature is a compact one.
+// On the way: the words [0, idle_n) of the OTHER counter array — the previous slot build's counts, which nobody reads any more —
+// are cleared for the next build (Scope::KEEP_SLOT), and the first thread writes the build's eight device flags from the stamps
+// of k_assign, as the scan of a compact build does.
+__global__ __launch_bounds__(256) void k_sort_slots(const unsigned *__restrict__ count, int *__restrict__ slots, int64_t ncell,
+                                                    unsigned *__restrict__ idle, int64_t idle_n, unsigned *__restrict__ ctl, unsigned gen,
+                                                    int *__restrict__ big_sink, int *__restrict__ flags, int64_t slot_hi)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c == 0) {
+        flags[0] = ctl[1] == gen ? 1 : 0; flags[1] = 0; flags[2] = 0; flags[3] = 0;
+        flags[4] = ctl[2] == gen ? 1 : 0; flags[5] = 0; flags[6] = 0; flags[7] = 0;
+    }
+    if (c < idle_n) idle[c] = 0u;
+    if (c >= ncell)
+        return;
+    const int full = (int)count[c];
+    if (full > SLOT_CAP) report_big_cell(ctl, gen, big_sink, full);
+    const int n = min(full, SLOT_CAP);
+    if (n <= 1)
+        return;
+    int4 *cell = reinterpret_cast<int4 *>(slots + 4 * c), *cell_hi = reinterpret_cast<int4 *>(slots + slot_hi + 4 * c); // (slots is 256-byte aligned, slot_hi a multiple of four)
+    auto ce = [](int &a, int &b) { const int hi = max(a, b), lo = min(a, b); a = hi; b = lo; }; // a >= b afterwards
+    int4 q0 = cell[0];
+    int id[8] = {q0.x, n > 1 ? q0.y : INT32_MIN, n > 2 ? q0.z : INT32_MIN, n > 3 ? q0.w : INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN};
+    if (SLOT_CAP == 4 || n <= 4) {
+        ce(id[0], id[1]); ce(id[2], id[3]); ce(id[0], id[2]); ce(id[1], id[3]); ce(id[1], id[2]);
+        cell[0] = make_int4(id[0], id[1], id[2], id[3]);
+        return;
+    }
+    const int4 q1 = cell_hi[0];
+    id[4] = q1.x; id[5] = n > 5 ? q1.y : INT32_MIN; id[6] = n > 6 ? q1.z : INT32_MIN; id[7] = n > 7 ? q1.w : INT32_MIN;
+    ce(id[0], id[1]); ce(id[2], id[3]); ce(id[4], id[5]); ce(id[6], id[7]); // Batcher's odd-even merge sort of eight (sort_cell_net)
+    ce(id[0], id[2]); ce(id[1], id[3]); ce(id[4], id[6]); ce(id[5], id[7]);
+    ce(id[1], id[2]); ce(id[5], id[6]);
+    ce(id[0], id[4]); ce(id[1], id[5]); ce(id[2], id[6]); ce(id[3], id[7]);
+    ce(id[2], id[4]); ce(id[3], id[5]);
+    ce(id[1], id[2]); ce(id[3], id[4]); ce(id[5], id[6]);
+    cell[0] = make_int4(id[0], id[1], id[2], id[3]);
+    cell_hi[0] = make_int4(id[4], id[5], id[6], id[7]);
 }
 
 __global__ __launch_bounds__(256) void k_gather(const double *__restrict__ x, const double *__restrict__ y,
@@ -682,6 +760,71 @@ __global__ __launch_bounds__(1024) void k_order_far_flag(const double *__restric
     if (threadIdx.x == 0) *flag = 4 * s_far > 1024 ? 1 : 0;
 }
 
+// ----------------------------------------------------------------------------
+// The slot grid's host state
+// ----------------------------------------------------------------------------
+// 1: neighbor builds may bin straight into cell slots (CellGrid::slot_cap); 0: the compact grid always (mdh_debug_set_slot_grid)
+static std::atomic<int> g_slot_grid{[] { const char *e = std::getenv("MDH_SLOT_GRID"); return e ? std::atoi(e) : 1; }()};
+// MDH_SLOT_GRID_FORCE=1 (a measuring switch, profiles/slot_grid.md): the slot grid wherever its layout allows, whatever the history
+// says — what a build that meets full cells costs (spill list, listed tiles, the thread-per-atom mop-up); results are the same
+static const bool g_slot_force = [] { const char *e = std::getenv("MDH_SLOT_GRID_FORCE"); return e && std::atoi(e) != 0; }();
+static std::atomic<int> g_last_slot_build{0}; // the last FOR_ROWS build of the process was a slot build (mdh_debug_neighbor_plan)
+int last_grid_was_slot() { return g_last_slot_build.load(std::memory_order_relaxed); }
+static std::mutex g_slot_mu;
+// per (N, grid, device): two pinned words the device writes: host[0] = did the last FINISHED build of the signature see a cell of more
+// than SLOT_CAP atoms (1 / 0; -1: none has finished yet — the first builds of a signature are compact ones), host[1] = such a cell's count
+struct SlotHistory { int64_t N, ncell; int device; int *host; };
+// per KEEP_SLOT block: the half the next slot build counts into (all zero) and the words of each half that are not zero
+struct SlotBlock { void *p; int next; int64_t dirty[2]; };
+static std::vector<SlotHistory *> g_slot_hist;
+static std::atomic<SlotHistory *> g_last_hist{nullptr}; // the signature of the last build that kept a history (mdh_debug_slot_grid_counters)
+static std::vector<SlotBlock *> g_slot_blocks;
+
+static int slot_history(int64_t N, int64_t ncell, SlotHistory **out)
+{
+    int device = 0;
+    (void)hipGetDevice(&device);
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    for (SlotHistory *h : g_slot_hist)
+        if (h->N == N && h->ncell == ncell && h->device == device) { *out = h; return MDH_OK; }
+    SlotHistory *h = nullptr;
+    if (g_slot_hist.size() >= 64) {
+        // the oldest signature hands its entry and its pinned words on (grid_stats_hint does the same).  A build of that old signature
+        // may still be in flight and write its answer into them: the new signature then reads a wrong history once, which picks a
+        // path, never a result
+        h = g_slot_hist.front();
+        g_slot_hist.erase(g_slot_hist.begin());
+    } else {
+        int *host = nullptr;
+        MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&host), 2 * sizeof(int), hipHostMallocDefault));
+        h = new SlotHistory{};
+        h->host = host;
+    }
+    h->N = N; h->ncell = ncell; h->device = device;
+    h->host[0] = -1; h->host[1] = 0;
+    g_slot_hist.push_back(h);
+    *out = h;
+    return MDH_OK;
+}
+static SlotBlock *slot_block_state(void *p)
+{
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    for (SlotBlock *b : g_slot_blocks)
+        if (b->p == p) return b;
+    // (a kept block starts zero-filled.  Entries are never removed, not even when mdh_release_workspace frees the block: one per
+    // distinct block address, and an address that comes back names a new, zero-filled block, for which any entry is right — its
+    // "dirty" extent only makes the next sort clear more than it has to, within the block: build_cell_grid clamps it)
+    g_slot_blocks.push_back(new SlotBlock{p, 0, {0, 0}});
+    return g_slot_blocks.back();
+}
+
+bool slot_grid_rule(bool ordered, bool keyed, bool windowed, int row_width, int64_t ncell, int64_t N, bool seen, bool big, int listed)
+{
+    if (!ordered || keyed || windowed || row_width > 16) return false;
+    if (ncell > 2 * N || ncell * SLOT_CAP >= (int64_t(1) << 31)) return false; // (the slots are indexed with 32 bits; 32 bytes a cell)
+    return seen && !big && listed == 0;
+}
+
 int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b, const GridRequest &rq,
                     CellGrid &cg)
 {
@@ -693,24 +836,18 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
     const Grid &g = cg.g;
     hipStream_t st = sc.stream();
 
-    // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
-    // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
-    unsigned *cell_count = static_cast<unsigned *>(sc.alloc_kept(sizeof(unsigned) * (size_t)g.ncell, Scope::KEEP_ZERO));
-    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
-    cg.flags = sc.alloc_n<int>(8);
-    cg.cell_start = sc.alloc_n<int>((size_t)g.ncell + 1);
-    int2 *ent = sc.alloc_n<int2>((size_t)N); // (cell, slot) of every atom: k_assign -> k_scatter
-    int *rank = reinterpret_cast<int *>(ent); // ... and, once the atoms are scattered, the N ints of scratch of the in-cell sorts
-    cg.order = sc.alloc_n<int>((size_t)N + 4); // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
-    unsigned short *mv = sc.alloc_n<unsigned short>((size_t)N);
     cg.xs = cg.ys = cg.zs = nullptr;
     cg.mvs = nullptr;
     cg.pk = nullptr;
-    // scattered (FOR_ROWS_UNORDERED): the caller knows that the atoms come in no spatial order
-    CellGrid::Packed *rec = nullptr;
-    int *rec_flag = nullptr;
     cg.ix = cg.iy = cg.iz = nullptr;
     cg.imv = nullptr;
+    cg.slot_cap = 0; cg.spill = nullptr; cg.n_spill = nullptr; cg.n_binned = N;
+    cg.big_stamp = nullptr; cg.big_gen = 0; cg.big_sink = nullptr;
+    // what the atoms are wanted as — decided before anything is allocated: a slot grid has no entries, no prefix array and
+    // counters of its own
+    // scattered (FOR_ROWS_UNORDERED): the caller knows that the atoms come in no spatial order
+    int *rec_flag = nullptr;
+    bool indirect = false;
     if (packed) {
         // records: always for a caller that knows (scattered); for a large system otherwise when the last sample of this (N, grid) said so
         if (!scattered && N >= (int64_t(1) << 18)) {
@@ -722,7 +859,54 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
         // mdh_debug_set_indirect(0): the records always — an A/B switch, and how the tests reach both paths on one input
         // (not for dense cells — six atoms and more, the wide instance's ground: two workgroups per CU hide the staging's
         // dependent gathers badly, build_neighbor(5.0, 50) at 10 M atoms 4.48 -> 4.60 ms; profiles/r06_cell_grid_ab.txt)
-        const bool indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && rq.sort_desc && (double)N <= 6.0 * (double)g.ncell && rq.row_width <= 16;
+        indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && rq.sort_desc && (double)N <= 6.0 * (double)g.ncell && rq.row_width <= 16;
+    }
+    // The slot grid (CellGrid::slot_cap) where the rule allows.  What the rule asks of the signature's history comes from two
+    // pinned words: the in-cell sort of every build that could have been a slot build stamps one with its generation when it sees a
+    // cell of more than SLOT_CAP atoms, and the tile kernel's mop-up reports the tiles it was left (lane_listed_hint).  Both arrive
+    // when the device gets there: a build that reads an old answer is a slower one, never a wrong one.
+    SlotHistory *hist = nullptr;
+    bool slot = false;
+    const bool windows = window.set || centre.set;
+    if (packed && rq.slots_ok && slot_grid_rule(indirect, rq.sort_key != nullptr, windows, rq.row_width, g.ncell, N, true, false, 0)) {
+        MDH_TRY(slot_history(N, g.ncell, &hist));
+        g_last_hist.store(hist, std::memory_order_relaxed);
+        const int last = *(volatile int *)hist->host;
+        const bool seen = last >= 0, big = last > 0;
+        slot = g_slot_grid.load(std::memory_order_relaxed) != 0 && (g_slot_force ||
+               slot_grid_rule(indirect, rq.sort_key != nullptr, windows, rq.row_width, g.ncell, N, seen, big, lane_listed_hint(N, g.ncell)));
+    }
+    // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
+    // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
+    // (a slot build: the half of a KEEP_SLOT block that the previous slot build's sort cleared, 64 words of header — [0] the length
+    // of the spill list — and the counters behind them)
+    unsigned *cell_count = nullptr, *slot_block = nullptr, *slot_idle = nullptr;
+    int64_t slot_idle_n = 0;
+    SlotBlock *sb = nullptr;
+    if (slot) {
+        // (+ 64 words behind the counts: the tile kernel reads a cell's count with the word behind it)
+        slot_block = static_cast<unsigned *>(sc.alloc_kept(2 * sizeof(unsigned) * (size_t)(g.ncell + 128), Scope::KEEP_SLOT));
+        if (slot_block) {
+            const size_t half = sc.held_bytes(slot_block) / 8; // words of a half (a block is a multiple of 256 bytes)
+            sb = slot_block_state(slot_block);
+            cell_count = slot_block + (size_t)sb->next * half + 64;
+            slot_idle = slot_block + (size_t)(1 - sb->next) * half;
+            slot_idle_n = std::min<int64_t>(sb->dirty[1 - sb->next], (int64_t)half); // (a freed block's address may come back as a smaller, zero-filled one)
+        }
+    } else {
+        cell_count = static_cast<unsigned *>(sc.alloc_kept(sizeof(unsigned) * (size_t)g.ncell, Scope::KEEP_ZERO));
+    }
+    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
+    cg.flags = sc.alloc_n<int>(8);
+    cg.cell_start = slot ? reinterpret_cast<int *>(cell_count) : sc.alloc_n<int>((size_t)g.ncell + 1);
+    int2 *ent = sc.alloc_n<int2>((size_t)N); // (cell, slot) of every atom: k_assign -> k_scatter; a slot build: its spill list
+    int *rank = reinterpret_cast<int *>(ent); // ... and, once the atoms are scattered, the N ints of scratch of the in-cell sorts
+    // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
+    cg.order = sc.alloc_n<int>(slot ? (size_t)g.ncell * SLOT_CAP + 4 : (size_t)N + 4);
+    const int64_t slot_hi = 4 * g.ncell; // (a slot grid: where the second plane of four slots per cell starts)
+    unsigned short *mv = sc.alloc_n<unsigned short>((size_t)N);
+    CellGrid::Packed *rec = nullptr;
+    if (packed) {
         if (!indirect) cg.pk = sc.alloc_n<CellGrid::Packed>((size_t)N);
         if (scattered) rec = sc.alloc_n<CellGrid::Packed>((size_t)N);
     } else {
@@ -793,12 +977,38 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
     // throughput — 413 -> 440 on a shuffled frame, which therefore keeps one: profiles/r05_assign_k.txt)
     const bool assign4 = N >= (int64_t)1 << 20 && !scattered;
 #define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)rq.wrap_first, ent, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
+#define MDH_ASSIGN_SLOT(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K, true>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)rq.wrap_first, (int2 *)nullptr, cell_count, ctl, gen, slack, mv, win, rec, 1, cg.order, ent, cell_count - 64, slot_hi)
+    if (slot) {
+        // bin, sort in place, done: no scan, no scatter, no gather (the atoms stay where the caller has them, CellGrid::ix)
+        if (b.tri) { if (assign4) MDH_ASSIGN_SLOT(true, 4); else MDH_ASSIGN_SLOT(true, 1); }
+        else { if (assign4) MDH_ASSIGN_SLOT(false, 4); else MDH_ASSIGN_SLOT(false, 1); }
+        hipLaunchKernelGGL(k_sort_slots, dim3(grid_for(std::max<int64_t>(g.ncell, slot_idle_n), 256)), dim3(256), 0, st, cell_count, cg.order, g.ncell,
+                           slot_idle, slot_idle_n, ctl, gen, hist->host, cg.flags, slot_hi);
+        MDH_HIP(hipGetLastError());
+        {
+            std::lock_guard<std::mutex> lk(g_slot_mu);
+            sb->dirty[1 - sb->next] = 0;          // cleared by the sort above
+            sb->dirty[sb->next] = g.ncell + 64;   // this build's header and counts: read until the next slot build's sort clears them
+            sb->next = 1 - sb->next;
+        }
+        sc.keep_confirm(slot_block);
+        cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist->host;
+        cg.slot_cap = SLOT_CAP;
+        cg.slot_hi = slot_hi;
+        cg.spill = ent;
+        cg.n_spill = cell_count - 64;
+        cg.ix = x; cg.iy = y; cg.iz = z; cg.imv = mv;
+        g_last_slot_build = 1;
+        return MDH_OK;
+    }
+    g_last_slot_build = 0;
     if (b.tri) {
         if (assign4) MDH_ASSIGN(true, 4); else MDH_ASSIGN(true, 1);
     } else {
         if (assign4) MDH_ASSIGN(false, 4); else MDH_ASSIGN(false, 1);
     }
 #undef MDH_ASSIGN
+#undef MDH_ASSIGN_SLOT
     auto scan_piece = [&](int64_t from, int64_t to, unsigned use_gen, int *flags) {
         launch_scan_gen(st, cell_count + from, cg.cell_start + from, to - from, ctl, use_gen, true, flags); // [to] = the piece's total
     };
@@ -841,7 +1051,10 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
         if (!windowed && !rq.sort_key && (double)N > 6.0 * (double)g.ncell) {
             hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rank);
         } else if (!windowed) {
-            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rq.sort_key, rank);
+            // (hist: this build could have been a slot build — it reports a cell of more than SLOT_CAP atoms as one would)
+            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rq.sort_key, rank, ctl, gen,
+                               hist ? hist->host : (int *)nullptr);
+            if (hist) { cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist->host; }
         } else {
             hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p1 - p0) * plane, 256)), dim3(256), 0, st, cg.cell_start + p0 * plane, cg.order, (p1 - p0) * plane, rq.sort_key, rank);
             if (p3 > p2)
@@ -889,6 +1102,28 @@ int mdh_cell_window_check(void *stream)
 }
 
 int mdh_debug_set_indirect(int on) { return g_indirect.exchange(on ? 1 : 0); }
+int mdh_debug_set_slot_grid(int on)
+{
+    if (on == 2) { // ... and every signature's history forgotten: its next build is a first one
+        std::lock_guard<std::mutex> lk(g_slot_mu);
+        for (SlotHistory *h : g_slot_hist) h->host[0] = -1; // (the caller has synchronised: no build is in flight)
+    }
+    return g_slot_grid.exchange(on ? 1 : 0);
+}
+int mdh_debug_slot_grid_counters(int64_t *out4)
+{
+    const SlotHistory *h = g_last_hist.load(std::memory_order_relaxed);
+    const int last = h ? ((const volatile int *)h->host)[0] : 0, big = h ? ((const volatile int *)h->host)[1] : 0;
+    out4[0] = last_grid_was_slot();
+    out4[1] = last > 0 ? 1 : 0;
+    out4[2] = out4[1] ? big : 0;
+    out4[3] = SLOT_CAP;
+    return MDH_OK;
+}
+int mdh_debug_slot_grid_rule(int ordered, int keyed, int windowed, int row_width, int64_t ncell, int64_t N, int seen, int big, int listed)
+{
+    return slot_grid_rule(ordered != 0, keyed != 0, windowed != 0, row_width, ncell, N, seen != 0, big != 0, listed) ? 1 : 0;
+}
 }
 
 MDH_WARM_UNIT(cell_grid)

@@ -147,11 +147,14 @@ class Scope {
     //   KEEP_SCAN : control words of the single-pass scan (a ticket that its last block resets, generation-stamped status
     //               words: a stale one is never mistaken for a fresh one)
     //   KEEP_TODO : word 0 (blocks done) and word 64 (length of a to-do list) zero when idle (reset by the list's last reader)
-    // keep_confirm(p): the kernels that restore p's invariant have been enqueued; a KEEP_ZERO / KEEP_TODO block that leaves
-    // its Scope unconfirmed (an error path) is zero-filled on the stream before it returns to the cache.
-    enum Keep { KEEP_NONE = 0, KEEP_ZERO = 1, KEEP_SCAN = 2, KEEP_TODO = 3 };
+    //   KEEP_SLOT : the two alternating counter arrays of a slot grid (cell_grid.hip): the half the next build counts into is
+    //               all zero when idle, the other holds the last build's counts until that next build's in-cell sort clears it
+    // keep_confirm(p): the kernels that restore p's invariant have been enqueued; a KEEP_ZERO / KEEP_TODO / KEEP_SLOT block that
+    // leaves its Scope unconfirmed (an error path) is zero-filled on the stream before it returns to the cache.
+    enum Keep { KEEP_NONE = 0, KEEP_ZERO = 1, KEEP_SCAN = 2, KEEP_TODO = 3, KEEP_SLOT = 4 };
     void *alloc_kept(size_t bytes, Keep tag);
     void keep_confirm(void *p);
+    size_t held_bytes(const void *p) const; // size of a block this Scope holds (a kept block may be larger than what was asked for)
 
     // Stage a caller array.  space==MDH_DEVICE: returns the pointer itself.
     // space==MDH_HOST: returns a device copy (uploaded when `in`), and remembers

@@ -58,7 +58,34 @@ struct CellGrid {
     // small gathers per atom where the record took two 16-byte reads — and the grid build is one pass over 56 B per atom shorter)
     const double *ix = nullptr, *iy = nullptr, *iz = nullptr;
     const unsigned short *imv = nullptr;
+    // SLOT GRID (slot_cap != 0; an indirect grid of a neighbor build whose cells were small last time, cell_grid.hip): the ids of
+    // cell c sit in fixed slots of `order`, DESCENDING, where the cell's atomic counter placed them — no prefix sum, no second
+    // scatter.  Two planes of four slots per cell (slot_pos): the first four ids at order[4 c ...], the next four at
+    // order[slot_hi + 4 c ...] — a lattice's cells hold one, two or four atoms and touch the first plane only, half the bytes of
+    // eight slots side by side (profiles/slot_grid.md).  cell_start then holds the ncell per-cell COUNTS (no [ncell] entry); a count
+    // keeps running past slot_cap, and the atoms it could not place are (cell, id) entries of the spill list, in no order.
+    int slot_cap = 0;
+    int64_t slot_hi = 0;              // first entry of the second plane (4 ncell)
+    const int2 *spill = nullptr;      // [N]
+    const unsigned *n_spill = nullptr; // device counter: entries of spill
+    int64_t n_binned = 0;             // slot grid: atoms handed to the build (absent ones, x = NaN, included: they take no cell)
+    // a build that keeps the slot grid's history (cell_grid.hip SlotHistory): its in-cell sort stamps *big_stamp with big_gen when it sees
+    // a cell of more than SLOT_CAP atoms; the LAST kernel of the pass over the grid turns that into the signature's pinned word
+    // (TileFilter::big_sink: 1 or 0 — a definite answer per finished build, so a host that runs many builds ahead reads the last one)
+    const unsigned *big_stamp = nullptr;
+    unsigned big_gen = 0;
+    int *big_sink = nullptr;
 };
+// atoms a cell of a slot grid holds in place (two planes of four ids, slot_pos); MDH_SLOT_CAP=4 is the measuring build of profiles/slot_grid.md
+#ifndef MDH_SLOT_CAP
+#define MDH_SLOT_CAP 8
+#endif
+constexpr int SLOT_CAP = MDH_SLOT_CAP;
+static_assert(SLOT_CAP == 4 || SLOT_CAP == 8, "a cell's slots are one or two 16-byte loads");
+// position in CellGrid::order of slot k (< SLOT_CAP) of cell c; hi: CellGrid::slot_hi
+__host__ __device__ __forceinline__ int64_t slot_pos(int64_t c, int k, int64_t hi) { return c * 4 + k + (k >= 4 ? hi - 4 : 0); }
+// the second plane and the spill list of a slot grid, as the thread-per-atom kernels see them (neighbor.hip)
+struct SlotSpill { const int2 *list = nullptr; const unsigned *n = nullptr; int64_t hi = 0; };
 // a cell-sorted atom, from either representation
 struct SortedView {
     const double *xs, *ys, *zs;
@@ -100,6 +127,7 @@ struct TileFilter {
     int tile = 1, tile_z = 1;
     int nt[3] = {1, 1, 1};
     int *listed_sink = nullptr; // != nullptr: the list is the tile kernel's FIRST pass's (no slice pass ran); the mop-up writes its length here (GridStats::listed_sink)
+    const unsigned *big_stamp = nullptr; unsigned big_gen = 0; int *big_sink = nullptr; // CellGrid::big_sink: published by the pass's last kernel
 };
 // occupied_cells: cells that hold atoms (occupied_cells_hint); 0 = assume all of them
 TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells);
@@ -147,6 +175,7 @@ struct LanePlan {
 };
 int grid_stats_hint(Scope &sc, const CellGrid &cg, int64_t N, GridStats *out);
 LanePlan plan_lane(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count);
+int lane_listed_hint(int64_t N, int64_t ncell); // tiles the last finished build of this (N, grid) listed; -1: not known (cell_grid.hip: the slot grid's taking rule)
 int lane_last_listed(); // tiles listed for the slice pass as last seen when a plan was made (mdh_debug_counters)
 int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, int64_t N, const DBox &b, double rc,
                          const RowsRequest &rows, TileFilter &tf);
@@ -224,7 +253,14 @@ struct GridRequest {
     // wide instance, which hides the indirect staging's gathers badly (two or three workgroups per CU): such a build keeps the
     // records (the 12-nearest search's cutoff build, 4.7 atoms per cell, rows of 24: 2.15 ms with records, 2.22 without)
     int row_width = 0;
+    // FOR_ROWS: the atoms may also be wanted as a SLOT GRID (CellGrid::slot_cap) where slot_grid_rule() allows: every kernel behind
+    // neighbor_pass reads both forms
+    bool slots_ok = false;
 };
+// cell_grid.hip: may this build bin straight into cell slots?  (host only; exported as mdh_debug_slot_grid_rule for the table test)
+// ordered: the ix form would be taken; keyed: a sort_key; windowed: a pending cell or centre window; seen: a build of this (N, grid)
+// has reported; big: that build saw a cell of more than SLOT_CAP atoms; listed: tiles it listed (-1: not known)
+bool slot_grid_rule(bool ordered, bool keyed, bool windowed, int row_width, int64_t ncell, int64_t N, bool seen, bool big, int listed);
 // Bins the atoms into cg.g (dims/mode set by the caller) and produces cell_start/order and the atoms as rq.atoms says; takes the
 // thread's pending window hints (mdh_hint_cell_window, mdh_hint_centre_window), whatever the build is for
 int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b, const GridRequest &rq,

@@ -25,16 +25,102 @@ int g_neighbor_variant = 0; // 0 = automatic, 1 = force the thread-per-atom kern
 //   MODE 2: also write the pads   (-1, rc+1)
 // ----------------------------------------------------------------------------
 // one centre atom (position p of the cell-sorted arrays): the reference's 27-cell walk, neighbor.cpp:139-177
-template <bool TRI, int MODE>
+// The cell view has two forms (template SLOT).  Compact: position p of the cell order names an atom, a cell is the range
+// [cell_start[c], cell_start[c + 1]) of it, and the three cells of a z-run are one range.  Slot grid (CellGrid::slot_cap): cell_start[c]
+// is the cell's COUNT, its first SLOT_CAP ids sit in descending order in the cell's slots of `order` (two planes of four, slot_pos:
+// order[4 c + k] and order[4 ncell + 4 c + k - 4]), the three cells of a run are walked one by one, centres are named by their id (p = id: the atoms are the caller's arrays), and a cell whose count ran past
+// SLOT_CAP has the rest of its atoms on the spill list.
+//
+// the largest id below `prev` among the atoms of an overflowed cell — its slots and its entries of the spill list — or -1: a
+// selection walk, one pass over the (short) list per candidate; the rare path, and the next build of the signature is a compact one
+__device__ __forceinline__ int next_id_below(const SortedView &sv, const SlotSpill &sp, int64_t cell, int prev)
+{
+    int best = -1;
+    for (int u = 0; u < SLOT_CAP; ++u) {
+        const int v = sv.order[slot_pos(cell, u, sp.hi)];
+        if (v < prev && v > best) best = v;
+    }
+    const unsigned ns = *sp.n;
+    for (unsigned w = 0; w < ns; ++w) {
+        const int2 e = sp.list[w];
+        if ((int64_t)e.x == cell && e.y < prev && e.y > best) best = e.y;
+    }
+    return best;
+}
+// the k-th atom of a cell of a slot grid, in any fixed order (centres: every atom of the cell once); -1: none
+__device__ __forceinline__ int slot_cell_atom(const SortedView &sv, const SlotSpill &sp, int64_t cell, int k)
+{
+    if (k < SLOT_CAP)
+        return sv.order[slot_pos(cell, k, sp.hi)];
+    k -= SLOT_CAP;
+    const unsigned ns = *sp.n;
+    for (unsigned w = 0; w < ns; ++w) {
+        const int2 e = sp.list[w];
+        if ((int64_t)e.x == cell && k-- == 0) return e.y;
+    }
+    return -1;
+}
+
+template <bool TRI, int MODE, bool SLOT = false>
 __device__ __forceinline__ int neighbor_one(const SortedView &sv, const int *__restrict__ cell_start, const DBox &b,
                                             const Grid &g, double rc, int *__restrict__ verlet, double *__restrict__ dist,
                                             int *__restrict__ nn, int64_t M, int64_t p, double xi, double yi, double zi, int c0, int c1,
-                                            int c2)
+                                            int c2, const SlotSpill &sp = SlotSpill{})
 {
     int cnt = 0;
-    const int i = sv.id_of(p);
+    const int i = SLOT ? (int)p : sv.id_of(p);
     const double rcsq = rc * rc; // neighbor.cpp:127
     const int64_t row = (int64_t)i * M;
+    if constexpr (SLOT) {
+        auto candidate = [&](int j, double xq, double yq, double zq) {
+            if (j == i)
+                return;
+            double dx = xq - xi, dy = yq - yi, dz = zq - zi; // raw x[j] - wrapped centre, :164-166
+            pbc<TRI>(b, dx, dy, dz);
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            if (d2 <= rcsq) {
+                if (MODE != 0 && cnt < M) {
+                    verlet[row + cnt] = j;
+                    dist[row + cnt] = sqrt(d2);
+                }
+                ++cnt;
+            }
+        };
+        for (int a = c0 - 1; a <= c0 + 1; ++a) { // neighbor.cpp:147-151
+            const int ca = pmod(a, g.nc[0]);
+            for (int bb = c1 - 1; bb <= c1 + 1; ++bb) {
+                const int64_t base = ((int64_t)ca * g.nc[1] + pmod(bb, g.nc[1])) * g.nc[2];
+                for (int seg = 0; seg < 3; ++seg) {
+                    const int64_t cell = base + pmod(c2 - 1 + seg, g.nc[2]);
+                    const int n = cell_start[cell];
+                    if (n > SLOT_CAP) { // descending id over the slots and the spill list
+                        for (int j = next_id_below(sv, sp, cell, 0x7fffffff); j >= 0; j = next_id_below(sv, sp, cell, j))
+                            candidate(j, sv.xs[j], sv.ys[j], sv.zs[j]);
+                        continue;
+                    }
+                    for (int k0 = 0; k0 < n; k0 += 4) { // (four candidates per trip, as below: one plane of the cell's slots)
+                        double xq[4], yq[4], zq[4];
+                        int jq[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            sv.get(slot_pos(cell, min(k0 + u, n - 1), sp.hi), xq[u], yq[u], zq[u], jq[u]);
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            if (k0 + u < n) candidate(jq[u], xq[u], yq[u], zq[u]);
+                    }
+                }
+            }
+        }
+        nn[i] = cnt;
+        if (MODE == 2) {
+            const double pad = rc + 1.0;
+            for (int64_t n = cnt; n < M; ++n) {
+                verlet[row + n] = -1;
+                dist[row + n] = pad;
+            }
+        }
+        return cnt;
+    }
     const bool zrun = (c2 >= 1) && (c2 + 1 < g.nc[2]); // the three z-cells are one contiguous run
     for (int a = c0 - 1; a <= c0 + 1; ++a) {            // neighbor.cpp:147-151
         const int ca = pmod(a, g.nc[0]);
@@ -92,17 +178,74 @@ __device__ __forceinline__ int neighbor_one(const SortedView &sv, const int *__r
 // The same walk by a whole wavefront for ONE atom: 64 candidates per trip, the hits' slots from a ballot (candidate order = row
 // order, as above).  For the listed tiles of the mop-up kernel: their atoms sit in the fat last cells of the box, a thread walks
 // 300 ... 1000 candidates there four at a time (80 ... 380 dependent trips), a wave 9 runs of one to three trips.
-template <bool TRI, int MODE>
+template <bool TRI, int MODE, bool SLOT = false>
 __device__ __forceinline__ int neighbor_one_wave(const SortedView &sv, const int *__restrict__ cell_start, const DBox &b,
                                                  const Grid &g, double rc, int *__restrict__ verlet, double *__restrict__ dist,
                                                  int *__restrict__ nn, int64_t M, int64_t p, double xi, double yi, double zi, int c0,
-                                                 int c1, int c2)
+                                                 int c1, int c2, const SlotSpill &sp = SlotSpill{})
 {
     const int lane = (int)(threadIdx.x & 63);
     int cnt = 0;
-    const int i = sv.id_of(p);
+    const int i = SLOT ? (int)p : sv.id_of(p);
     const double rcsq = rc * rc; // neighbor.cpp:127
     const int64_t row = (int64_t)i * M;
+    if constexpr (SLOT) { // (the cell view's slot form, neighbor_one: a cell is one trip of the wave)
+        for (int a = c0 - 1; a <= c0 + 1; ++a) { // neighbor.cpp:147-151
+            const int ca = pmod(a, g.nc[0]);
+            for (int bb = c1 - 1; bb <= c1 + 1; ++bb) {
+                const int64_t base = ((int64_t)ca * g.nc[1] + pmod(bb, g.nc[1])) * g.nc[2];
+                for (int seg = 0; seg < 3; ++seg) {
+                    const int64_t cell = base + pmod(c2 - 1 + seg, g.nc[2]);
+                    const int n = cell_start[cell];
+                    if (n > SLOT_CAP) {
+                        // an overflowed cell: every lane walks the same candidates in descending id (next_id_below), lane 0 writes
+                        for (int j = next_id_below(sv, sp, cell, 0x7fffffff); j >= 0; j = next_id_below(sv, sp, cell, j)) {
+                            double dx = sv.xs[j] - xi, dy = sv.ys[j] - yi, dz = sv.zs[j] - zi;
+                            pbc<TRI>(b, dx, dy, dz);
+                            const double d2 = dx * dx + dy * dy + dz * dz;
+                            if (j != i && d2 <= rcsq) {
+                                if (MODE != 0 && lane == 0 && cnt < M) {
+                                    verlet[row + cnt] = j;
+                                    dist[row + cnt] = sqrt(d2);
+                                }
+                                ++cnt;
+                            }
+                        }
+                        continue;
+                    }
+                    bool hit = false;
+                    int j = -1;
+                    double d2 = 0.0;
+                    if (lane < n) {
+                        double xq, yq, zq;
+                        sv.get(slot_pos(cell, lane, sp.hi), xq, yq, zq, j);
+                        double dx = xq - xi, dy = yq - yi, dz = zq - zi; // raw x[j] - wrapped centre, :164-166
+                        pbc<TRI>(b, dx, dy, dz);
+                        d2 = dx * dx + dy * dy + dz * dz;
+                        hit = j != i && d2 <= rcsq;
+                    }
+                    const unsigned long long m = __ballot(hit);
+                    if (MODE != 0 && hit) {
+                        const int slot = cnt + __popcll(m & ((1ull << lane) - 1ull));
+                        if (slot < M) {
+                            verlet[row + slot] = j;
+                            dist[row + slot] = sqrt(d2);
+                        }
+                    }
+                    cnt += __popcll(m);
+                }
+            }
+        }
+        if (lane == 0) nn[i] = cnt;
+        if (MODE == 2) {
+            const double pad = rc + 1.0;
+            for (int64_t n = cnt + lane; n < M; n += 64) {
+                verlet[row + n] = -1;
+                dist[row + n] = pad;
+            }
+        }
+        return cnt;
+    }
     const bool zrun = (c2 >= 1) && (c2 + 1 < g.nc[2]);
     for (int a = c0 - 1; a <= c0 + 1; ++a) { // neighbor.cpp:147-151
         const int ca = pmod(a, g.nc[0]);
@@ -155,12 +298,12 @@ __device__ __forceinline__ int neighbor_one_wave(const SortedView &sv, const int
     return cnt;
 }
 
-template <bool TRI, int MODE>
+template <bool TRI, int MODE, bool SLOT = false>
 __device__ __forceinline__ void neighbor_atoms_body(const SortedView &sv,
                                                   const int *__restrict__ cell_start, int64_t N, const DBox &b, const Grid &g,
                                                   double rc, int *__restrict__ verlet, double *__restrict__ dist,
                                                   int *__restrict__ nn, int64_t M, int *__restrict__ max_count,
-                                                  const TileFilter &tf)
+                                                  const TileFilter &tf, const SlotSpill &sp = SlotSpill{})
 {
     const bool take_all = tf.moved && *tf.moved != 0; // the tiled kernel stood down: this kernel does the whole call
     if (tf.flag && !take_all && (tf.list || *tf.any == 0)) // nothing to mop up here (flagged tiles go to k_neighbor_tiles when listed)
@@ -170,14 +313,20 @@ __device__ __forceinline__ void neighbor_atoms_body(const SortedView &sv,
     // a workgroup strides over the atoms
     // (cell_start[ncell] = the atoms the grid holds: N, or fewer after a windowed build that dropped atoms outside its window —
     // the records behind them were never written)
-    N = min(N, (int64_t)cell_start[g.ncell]);
+    // (a slot grid: the centres are taken by id from the caller's arrays — its atoms are in a spatial order already; an absent atom,
+    // x = NaN, has no cell and gets no row)
+    if (!SLOT) N = min(N, (int64_t)cell_start[g.ncell]);
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < N; base += (int64_t)gridDim.x * blockDim.x) {
         const int64_t p = base + threadIdx.x;
         bool mine = p < N;
         int c0 = 0, c1 = 0, c2 = 0;
         double xi = 0, yi = 0, zi = 0;
+        if (SLOT && mine) {
+            xi = sv.xs[p]; yi = sv.ys[p]; zi = sv.zs[p];
+            mine = xi == xi;
+        }
         if (mine) {
-            { int idp; sv.get(p, xi, yi, zi, idp); }
+            if (!SLOT) { int idp; sv.get(p, xi, yi, zi, idp); }
             if (b.anypbc) // neighbor.cpp:139-142
                 wrap<TRI>(b, xi, yi, zi);
             cell_coords<TRI>(b, g, xi, yi, zi, c0, c1, c2);
@@ -187,8 +336,8 @@ __device__ __forceinline__ void neighbor_atoms_body(const SortedView &sv,
             }
         }
         if (mine) {
-            cnt = max(cnt, neighbor_one<TRI, MODE>(sv, cell_start, b, g, rc, verlet, dist, nn, M, p, xi, yi, zi, c0, c1, c2));
-            if (tf.cna_todo) defer(tf.cna_todo, sv.id_of(p));
+            cnt = max(cnt, neighbor_one<TRI, MODE, SLOT>(sv, cell_start, b, g, rc, verlet, dist, nn, M, p, xi, yi, zi, c0, c1, c2, sp));
+            if (tf.cna_todo) defer(tf.cna_todo, SLOT ? (int)p : sv.id_of(p));
         }
     }
     if (MODE == 0) {
@@ -205,19 +354,22 @@ __device__ __forceinline__ void neighbor_atoms_body(const SortedView &sv,
 
 // mop-up of the tiles the wave kernel listed (halo over the LDS budget, atoms far outside the box): a workgroup per listed
 // tile, its threads over the tile's centre atoms — the cost follows the number of listed tiles, not N
-template <bool TRI, int MODE>
+template <bool TRI, int MODE, bool SLOT = false>
 __global__ __launch_bounds__(256) void k_neighbor(SortedView sv, const int *__restrict__ cell_start, int64_t N, DBox b, Grid g, double rc,
                                                   int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn, int64_t M,
-                                                  int *__restrict__ max_count, TileFilter tf)
+                                                  int *__restrict__ max_count, TileFilter tf, SlotSpill sp)
 {
-    neighbor_atoms_body<TRI, MODE>(sv, cell_start, N, b, g, rc, verlet, dist, nn, M, max_count, tf);
+    if (tf.big_sink && blockIdx.x == 0 && threadIdx.x == 0)
+        *tf.big_sink = *tf.big_stamp == tf.big_gen ? 1 : 0; // (pinned host memory: the history of the slot grid, CellGrid::big_sink)
+    neighbor_atoms_body<TRI, MODE, SLOT>(sv, cell_start, N, b, g, rc, verlet, dist, nn, M, max_count, tf, sp);
 }
 
-template <bool TRI, int MODE>
+template <bool TRI, int MODE, bool SLOT = false>
 __device__ __forceinline__ void neighbor_tiles_body(const SortedView &sv,
                                                         const int *__restrict__ cell_start, const DBox &b, const Grid &g, double rc,
                                                         int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn,
-                                                        int64_t M, int *__restrict__ max_count, const TileFilter &tf)
+                                                        int64_t M, int *__restrict__ max_count, const TileFilter &tf,
+                                                        const SlotSpill &sp = SlotSpill{})
 {
     if (tf.moved && *tf.moved != 0) // k_neighbor takes the whole call
         return;
@@ -238,6 +390,29 @@ __device__ __forceinline__ void neighbor_tiles_body(const SortedView &sv,
         const int a = t0 * tf.tile + colq / tf.tile, c = t1 * tf.tile + colq % tf.tile;
         if (a < g.nc[0] && c < g.nc[1]) {
             const int64_t col = ((int64_t)a * g.nc[1] + c) * g.nc[2];
+            if constexpr (SLOT) {
+                // the column's atoms cell by cell, numbered as they come (slot_cell_atom); this wave takes every
+                // (nwave * MOP_CHUNKS)-th of them, as below
+                int seen = 0;
+                for (int cz = z0; cz < z1; ++cz) {
+                    const int n = cell_start[col + cz];
+                    for (int k = 0; k < n; ++k, ++seen) {
+                        if (seen % (nwave * MOP_CHUNKS) != chunk * nwave + wave)
+                            continue;
+                        const int id = slot_cell_atom(sv, sp, col + cz, k);
+                        if (id < 0)
+                            continue;
+                        double xi = sv.xs[id], yi = sv.ys[id], zi = sv.zs[id];
+                        if (b.anypbc)
+                            wrap<TRI>(b, xi, yi, zi);
+                        int c0, c1, c2;
+                        cell_coords<TRI>(b, g, xi, yi, zi, c0, c1, c2);
+                        best = max(best, neighbor_one_wave<TRI, MODE, true>(sv, cell_start, b, g, rc, verlet, dist, nn, M, id, xi, yi, zi, c0, c1, c2, sp));
+                        if (tf.cna_todo && (threadIdx.x & 63) == 0) defer(tf.cna_todo, id);
+                    }
+                }
+                continue;
+            }
             const int s = cell_start[col + z0], e = cell_start[col + z1]; // the z-run of a column is contiguous
             for (int p = s + chunk * nwave + wave; p < e; p += nwave * MOP_CHUNKS) {
                 double xi, yi, zi;
@@ -259,25 +434,27 @@ __device__ __forceinline__ void neighbor_tiles_body(const SortedView &sv,
     }
 }
 
-template <bool TRI, int MODE>
+template <bool TRI, int MODE, bool SLOT = false>
 __global__ __launch_bounds__(256) void k_neighbor_tiles(SortedView sv, const int *__restrict__ cell_start, DBox b, Grid g, double rc,
                                                         int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn, int64_t M,
-                                                        int *__restrict__ max_count, TileFilter tf)
+                                                        int *__restrict__ max_count, TileFilter tf, SlotSpill sp)
 {
-    neighbor_tiles_body<TRI, MODE>(sv, cell_start, b, g, rc, verlet, dist, nn, M, max_count, tf);
+    neighbor_tiles_body<TRI, MODE, SLOT>(sv, cell_start, b, g, rc, verlet, dist, nn, M, max_count, tf, sp);
 }
 
 // the two stand-bys behind a tile kernel that lists its leftovers, as ONE launch (a launch that finds nothing to do costs
 // ~4 us): the whole call atom by atom if the tile kernel stood down (unwrapped input), else the listed tiles
-template <bool TRI, int MODE>
+template <bool TRI, int MODE, bool SLOT = false>
 __global__ __launch_bounds__(256) void k_neighbor_mop(SortedView sv, const int *__restrict__ cell_start, int64_t N, DBox b, Grid g, double rc,
                                                       int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn, int64_t M,
-                                                      int *__restrict__ max_count, TileFilter tf)
+                                                      int *__restrict__ max_count, TileFilter tf, SlotSpill sp)
 {
     if (tf.listed_sink && blockIdx.x == 0 && threadIdx.x == 0)
         *tf.listed_sink = min(*tf.any, tf.list_cap); // (pinned host memory: the next build of this (N, grid) launches the slice pass if anything was listed)
-    if (tf.moved && *tf.moved != 0) neighbor_atoms_body<TRI, MODE>(sv, cell_start, N, b, g, rc, verlet, dist, nn, M, max_count, tf);
-    else neighbor_tiles_body<TRI, MODE>(sv, cell_start, b, g, rc, verlet, dist, nn, M, max_count, tf);
+    if (tf.big_sink && blockIdx.x == 0 && threadIdx.x == 0)
+        *tf.big_sink = *tf.big_stamp == tf.big_gen ? 1 : 0; // (pinned host memory: the history of the slot grid, CellGrid::big_sink)
+    if (tf.moved && *tf.moved != 0) neighbor_atoms_body<TRI, MODE, SLOT>(sv, cell_start, N, b, g, rc, verlet, dist, nn, M, max_count, tf, sp);
+    else neighbor_tiles_body<TRI, MODE, SLOT>(sv, cell_start, b, g, rc, verlet, dist, nn, M, max_count, tf, sp);
 }
 
 template <int MODE>
@@ -287,17 +464,17 @@ static void launch_neighbor(hipStream_t st, const CellGrid &cg, int64_t N, const
     // behind a tile kernel that lists its leftovers this launch only stands by for unwrapped input (device flag): a small grid
     // then, whose workgroups stride over the atoms if they do have to take the call (10 -> 3 us when they leave at once)
     dim3 grid(std::min(grid_for(N, 256), tf.list ? 2048 : 8192)), block(256);
+    const SlotSpill sp{cg.spill, cg.n_spill, cg.slot_hi};
+    // (TRI, SLOT: the cell view's form, CellGrid::slot_cap)
+#define MDH_MOP(KERNEL, TRI, SLOT, ...) hipLaunchKernelGGL((KERNEL<TRI, MODE, SLOT>), grid, block, 0, st, view_of(cg), cg.cell_start, __VA_ARGS__, b, cg.g, rc, verlet, dist, nn, M, max_count, tf, sp)
     if (tf.list) { // behind a tile kernel with a list (at most list_cap entries): both stand-bys in one launch
-        if (b.tri)
-            hipLaunchKernelGGL((k_neighbor_mop<true, MODE>), grid, block, 0, st, view_of(cg), cg.cell_start, N, b, cg.g, rc, verlet, dist, nn, M, max_count, tf);
-        else
-            hipLaunchKernelGGL((k_neighbor_mop<false, MODE>), grid, block, 0, st, view_of(cg), cg.cell_start, N, b, cg.g, rc, verlet, dist, nn, M, max_count, tf);
+        if (cg.slot_cap) { if (b.tri) MDH_MOP(k_neighbor_mop, true, true, N); else MDH_MOP(k_neighbor_mop, false, true, N); }
+        else { if (b.tri) MDH_MOP(k_neighbor_mop, true, false, N); else MDH_MOP(k_neighbor_mop, false, false, N); }
         return;
     }
-    if (b.tri)
-        hipLaunchKernelGGL((k_neighbor<true, MODE>), grid, block, 0, st, view_of(cg), cg.cell_start, N, b, cg.g, rc, verlet, dist, nn, M, max_count, tf);
-    else
-        hipLaunchKernelGGL((k_neighbor<false, MODE>), grid, block, 0, st, view_of(cg), cg.cell_start, N, b, cg.g, rc, verlet, dist, nn, M, max_count, tf);
+    if (cg.slot_cap) { if (b.tri) MDH_MOP(k_neighbor, true, true, N); else MDH_MOP(k_neighbor, false, true, N); }
+    else { if (b.tri) MDH_MOP(k_neighbor, true, false, N); else MDH_MOP(k_neighbor, false, false, N); }
+#undef MDH_MOP
 }
 
 // ----------------------------------------------------------------------------
@@ -615,6 +792,7 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
     if (!cg.flags_fresh) MDH_HIP(hipMemsetAsync(cg.flags + 2, 0, sizeof(int) * 2, st)); // the tile lists of this pass (flags[0], unwrapped input, stays)
     cg.flags_fresh = false;
     TileFilter tf{};
+    tf.big_stamp = cg.big_stamp; tf.big_gen = cg.big_gen; tf.big_sink = cg.big_sink;
     bool done = false;
     if (g_neighbor_variant == 0) { // tile kernel (orthogonal and triclinic boxes); the thread-per-atom code below then only mops up what it listed
         GridStats gs;
@@ -628,7 +806,8 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
             out.labelled = cna;
         }
     }
-    if (!done && !count && g_neighbor_variant != 1 && !b.tri) { // cells too full for the kernel above (or forced): the round-1 tiled kernel
+    // cells too full for the kernel above (or forced): the round-1 tiled kernel (a slot grid it does not read: the thread-per-atom kernel then)
+    if (!done && !count && g_neighbor_variant != 1 && !b.tri && !cg.slot_cap) {
         int64_t occ = 0;
         MDH_TRY(occupied_cells_hint(sc, cg, N, &occ));
         const TiledPlan plan = plan_tiled(b, cg.g, N, rows.M, occ);
@@ -652,6 +831,7 @@ static GridRequest rows_grid(const int64_t *key, int64_t row_width)
     GridRequest rq;
     rq.wrap_first = rq.sort_desc = true; rq.sort_key = key; rq.atoms = GridRequest::FOR_ROWS;
     rq.row_width = (int)std::min<int64_t>(row_width, 1 << 20);
+    rq.slots_ok = true; // (every kernel behind neighbor_pass reads a slot grid)
     return rq;
 }
 

@@ -418,7 +418,10 @@ __device__ __forceinline__ CellGrid::Packed load_record(const CellGrid::Packed *
 // IND: the atoms are read through the cell-sorted id list from the caller's arrays (load_record)
 // (the walked instances that also label — the slice pass, a tile list longer than its launch: rare — take the registers they want:
 // held to 128 they spill a dozen to scratch memory, and a launch that reserves scratch is slower to start even when it finds no work)
-template <bool COUNT, bool TRI, bool LOOP, bool FCNA, bool TK8, bool IND = false>
+// SLOT (with IND): the grid is a slot grid (CellGrid::slot_cap): cell_start holds the cells' COUNTS — a halo cell is ONE 4-byte load —
+// and the cell's ids sit in fixed slots of the id list (slot_pos).  An instance of its own, not a launch-uniform switch: with
+// the switch every instance, the compact grid's too, ran 9 us (0.8 %) slower at the headline (profiles/slot_grid.md)
+template <bool COUNT, bool TRI, bool LOOP, bool FCNA, bool TK8, bool IND = false, bool SLOT = false>
 __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) void k_neighbor_lane(
     const CellGrid::Packed *__restrict__ pk, const int *__restrict__ cell_start, DBox b,
     Grid g, double rc, float negc, float W, int *__restrict__ verlet, double *__restrict__ dist, int *__restrict__ nn,
@@ -426,7 +429,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
     int nt1, int nt2, Shape ts, const int *__restrict__ tile_list, const int *__restrict__ n_live, int list_mode,
     int *__restrict__ max_count, int *__restrict__ flagged, const int *__restrict__ parent, int parent_nt2, int nsub,
     int flag_slot, int *__restrict__ pattern, int *__restrict__ cna_todo, int jt0, int rw, int tile_base, int *__restrict__ listed_sink,
-    int cen_lo, int cen_hi, IndirectSrc isrc)
+    int cen_lo, int cen_hi, IndirectSrc isrc, int slot_hi)
 {
     const int TXY = ts.txy, TZ = ts.tz;
     const int coded = IND ? flags[4] : 0; // (uniform) some atom was handed in outside the box: the image codes are read as well
@@ -502,18 +505,27 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
             const bool in1 = b.pbc[1] ? (g1 >= -1 && g1 <= g.nc[1]) : (g1 >= 0 && g1 < g.nc[1]);
             const bool in2 = b.pbc[2] ? (g2 >= -1 && g2 <= g.nc[2]) : (g2 >= 0 && g2 < g.nc[2]);
             if (in0 && in1 && in2) {
+                bool over = false;
                 const int a0 = g0 < 0 ? g0 + g.nc[0] : (g0 >= g.nc[0] ? g0 - g.nc[0] : g0);
                 const int a1 = g1 < 0 ? g1 + g.nc[1] : (g1 >= g.nc[1] ? g1 - g.nc[1] : g1);
                 const int a2 = g2 < 0 ? g2 + g.nc[2] : (g2 >= g.nc[2] ? g2 - g.nc[2] : g2);
                 const int c = (a0 * g.nc[1] + a1) * g.nc[2] + a2; // (the host refuses grids of 2^31 cells or more)
-                h.src = cell_start[c];
-                h.cnt = cell_start[c + 1] - h.src;
+                if (SLOT) { // the count, and the cell's first four ids at 4 c of the id list
+                    const int n = cell_start[c];
+                    h.src = c << 2;
+                    h.cnt = min(n, SLOT_CAP);
+                    over = n > SLOT_CAP; // the rest of its atoms are on the spill list: the tile is listed
+                } else {
+                    h.src = cell_start[c];
+                    h.cnt = cell_start[c + 1] - h.src;
+                }
                 // image of the candidate cell seen from an in-grid centre cell: below the box -> raw coordinates are ~+L
                 // away (n = +1); above -> n = -1
                 const int n0 = g0 < 0 ? 1 : (g0 >= g.nc[0] ? -1 : 0);
                 const int n1 = g1 < 0 ? 1 : (g1 >= g.nc[1] ? -1 : 0);
                 const int n2 = g2 < 0 ? 1 : (g2 >= g.nc[2] ? -1 : 0);
                 h.img = (n0 + 1) | ((n1 + 1) << 2) | ((n2 + 1) << 4);
+                if (SLOT && over) h.img |= 64; // (bit 6: no part of the image code, combine_codes reads bits 0-5)
                 h.edge = (!b.pbc[0] && (a0 == 0 || a0 == g.nc[0] - 1)) || (!b.pbc[1] && (a1 == 0 || a1 == g.nc[1] - 1)) ||
                          (!b.pbc[2] && (a2 == 0 || a2 == g.nc[2] - 1));
                 // (cen_lo, cen_hi: the planes of axis 0 whose atoms want rows — all of them, or the planes of a decomposed system's own slab:
@@ -569,6 +581,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
         bool ok = !(total > cap || ncentres > CEN_CAP); // else: listed for the next pass
         const bool no_centres = ncentres == 0;          // (uniform) a tile of ghost planes only: nothing to stage, nothing to list
         if (no_centres) ok = false;
+        if (SLOT && (img & 64)) s_flag[2] = 1; // a halo cell of a slot grid that overflowed (halo_of): listed, as a run too long for its mask is
         STAMP(2);
         // the 3-cell run around every cell that can be a column entry of a centre's walk (cells tid-1, tid, tid+1 are adjacent in z
         // and in LDS)
@@ -649,7 +662,8 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                     for (int v = 0; v < 4; ++v) { // twenty independent loads in flight
                         if (k == 0) { a[v] = pa[v]; bb[v] = pb[v]; c[v] = pc[v]; d[v] = pd[v]; m[v] = pm[v]; }
                         else {
-                            const int q = src + min(k + v, cnt - 1);
+                            const int kv = min(k + v, cnt - 1);
+                            const int q = src + kv + (SLOT && kv >= 4 ? slot_hi : 0); // (slot_hi: a slot grid's second plane of four ids per cell)
                             const CellGrid::Packed r = load_record<IND>(pk, isrc, q, coded);
                             a[v] = r.x; bb[v] = r.y; c[v] = r.z; d[v] = r.id; m[v] = r.code;
                         }
@@ -667,7 +681,8 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                     int nd[4], nm[4];
 #pragma unroll
                     for (int v = 0; v < 4; ++v) { // (unconditional: past the cell's end the last atom again, never staged)
-                        const int q = src + min(k + 4 + v, cnt - 1);
+                        const int kv = min(k + 4 + v, cnt - 1);
+                        const int q = src + kv + (SLOT && kv >= 4 ? slot_hi : 0);
                         const CellGrid::Packed r = load_record<IND>(pk, isrc, q, coded);
                         na[v] = r.x; nb[v] = r.y; nc[v] = r.z; nd[v] = r.id; nm[v] = r.code;
                     }
@@ -1087,8 +1102,19 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
 }
 
 // tiles with at least one centre atom: flag (one thread per tile), then an order-preserving compaction
+// atoms of the cells [z0, z1) of the column that starts at cell `col`: the z-run of a column is contiguous in a compact grid, a
+// slot grid (slot != 0) has the counts themselves in cell_start
+__device__ __forceinline__ int column_atoms(const int *__restrict__ cell_start, int64_t col, int z0, int z1, int slot)
+{
+    if (!slot)
+        return cell_start[col + z1] - cell_start[col + z0];
+    int n = 0;
+    for (int k = z0; k < z1; ++k) n += cell_start[col + k];
+    return n;
+}
+
 __global__ __launch_bounds__(256) void k_tile_live(const int *__restrict__ cell_start, Grid g, int nt0, int nt1, int nt2, Shape ts,
-                                                   unsigned *__restrict__ live)
+                                                   unsigned *__restrict__ live, int slot)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt0 * nt1 * nt2)
@@ -1099,7 +1125,7 @@ __global__ __launch_bounds__(256) void k_tile_live(const int *__restrict__ cell_
     for (int a = t0 * ts.txy; a < min((t0 + 1) * ts.txy, g.nc[0]) && !any; ++a)
         for (int c = t1 * ts.txy; c < min((t1 + 1) * ts.txy, g.nc[1]) && !any; ++c) {
             const int64_t col = ((int64_t)a * g.nc[1] + c) * g.nc[2];
-            any = cell_start[col + z1] > cell_start[col + z0]; // the z-run of a column is contiguous
+            any = column_atoms(cell_start, col, z0, z1, slot) > 0;
         }
     live[t] = any ? 1u : 0u;
 }
@@ -1118,7 +1144,7 @@ __global__ __launch_bounds__(256) void k_tile_compact(const unsigned *__restrict
 // with the same (N, grid) left in pinned memory — an MD-style sequence of calls never waits — and waits only the first
 // time it sees a new (N, grid).  A stale value costs speed, never correctness.
 // out[0] = occupied cells; out[1 + len] = number of runs of that length (len 0..96; out[98] = longer)
-__global__ __launch_bounds__(256) void k_grid_stats(const int *__restrict__ cell_start, Grid g, int *__restrict__ out)
+__global__ __launch_bounds__(256) void k_grid_stats(const int *__restrict__ cell_start, Grid g, int *__restrict__ out, int slot)
 {
     __shared__ int hist[GridStats::NBIN];
     for (int k = threadIdx.x; k < GridStats::NBIN; k += blockDim.x) hist[k] = 0;
@@ -1133,7 +1159,7 @@ __global__ __launch_bounds__(256) void k_grid_stats(const int *__restrict__ cell
         for (int a = b0 * 4; a < x1; ++a)
             for (int c = b1 * 4; c < y1; ++c) {
                 const int64_t col = ((int64_t)a * g.nc[1] + c) * g.nc[2];
-                any = any || cell_start[col + z1] > cell_start[col + z0];
+                any = any || column_atoms(cell_start, col, z0, z1, slot) > 0;
             }
         if (any) {
             mine += (x1 - b0 * 4) * (y1 - b1 * 4) * (z1 - z0);
@@ -1141,7 +1167,7 @@ __global__ __launch_bounds__(256) void k_grid_stats(const int *__restrict__ cell
                 for (int c = b1 * 4; c < y1; ++c) {
                     const int64_t col = ((int64_t)a * g.nc[1] + c) * g.nc[2];
                     for (int k = z0; k < z1; ++k) {
-                        const int len = cell_start[col + min(k + 2, g.nc[2])] - cell_start[col + max(k - 1, 0)];
+                        const int len = column_atoms(cell_start, col, max(k - 1, 0), min(k + 2, g.nc[2]), slot);
                         atomicAdd(&hist[1 + min(len, 97)], 1);
                     }
                 }
@@ -1176,7 +1202,7 @@ int grid_stats_hint(Scope &sc, const CellGrid &cg, int64_t N, GridStats *out)
             return sc.error();
         MDH_HIP(hipMemsetAsync(dcnt, 0, sizeof(int) * GridStats::NBIN, st));
         const int blocks = (int)std::min<int64_t>((cg.g.ncell / 64 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_grid_stats, dim3(blocks), dim3(256), 0, st, cg.cell_start, cg.g, dcnt);
+        hipLaunchKernelGGL(k_grid_stats, dim3(blocks), dim3(256), 0, st, cg.cell_start, cg.g, dcnt, cg.slot_cap);
         MDH_HIP(hipMemcpyAsync(host_dst, dcnt, sizeof(int) * GridStats::NBIN, hipMemcpyDeviceToHost, st));
         return MDH_OK;
     };
@@ -1415,7 +1441,7 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
         nt0_run = t_hi - t_lo + 1;
         per = (int)(((int64_t)nt0_run * nt[1] * nt[2] + 7) / 8);
     } else {
-        hipLaunchKernelGGL(k_tile_live, dim3(grid_for(ntiles, 256)), dim3(256), 0, st, cg.cell_start, cg.g, nt[0], nt[1], nt[2], ts, live);
+        hipLaunchKernelGGL(k_tile_live, dim3(grid_for(ntiles, 256)), dim3(256), 0, st, cg.cell_start, cg.g, nt[0], nt[1], nt[2], ts, live, cg.slot_cap);
         MDH_TRY(exclusive_scan_u32(sc, live, slot, ntiles)); // slot[ntiles] = number of live tiles
         hipLaunchKernelGGL(k_tile_compact, dim3(grid_for(ntiles, 256)), dim3(256), 0, st, live, slot, (int)ntiles, tile_list);
         // live tiles expected from the last known occupancy (+25 %); a workgroup takes further tiles of its chunk if that was too few
@@ -1438,18 +1464,20 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
     const Shape ts2 = make_shape(ts.txy, 1, nt[1], nt2b);
     const bool indirect = !cg.pk; // CellGrid::ix
     const lane::IndirectSrc isrc{cg.ix, cg.iy, cg.iz, cg.imv, cg.order};
-#define MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, IND, GRID, JT0, ...)                                                                 \
+    const int slot_hi = cg.slot_cap ? (int)(cg.slot_hi - 4) : 0; // a slot grid: id k >= 4 of cell c at 4 c + k + slot_hi (slot_pos); 0: compact
+#define MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, IND, SLOT, GRID, JT0, ...)                                                                 \
     do {                                                                                                                                  \
         if (lds > 60 * 1024) /* above the default dynamic-LDS limit: raise it for the instance about to run */                            \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND>), GRID, dim3(NW * 64), lds, st, cg.pk, cg.cell_start, b, \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND, SLOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND, SLOT>), GRID, dim3(NW * 64), lds, st, cg.pk, cg.cell_start, b, \
                            cg.g, rc, negc, plan.T, verlet, dist, nn, Mi, wp, plan.cap, cg.flags, nullptr, __VA_ARGS__, pattern, tf.cna_todo, JT0, plan.rw, tile_base, plan.listed_sink, \
-                           cen_lo, cen_hi, isrc); \
+                           cen_lo, cen_hi, isrc, slot_hi); \
     } while (0)
 #define MDH_LANE_PASS(COUNT, TRI, LOOP, FCNA, TK8, GRID, JT0, ...)                                                                        \
     do {                                                                                                                                  \
-        if (indirect) MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, true, GRID, JT0, __VA_ARGS__);                                         \
-        else MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, false, GRID, JT0, __VA_ARGS__);                                                 \
+        if (indirect && cg.slot_cap) MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, true, true, GRID, JT0, __VA_ARGS__);                    \
+        else if (indirect) MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, true, false, GRID, JT0, __VA_ARGS__);                             \
+        else MDH_LANE_PASS_I(COUNT, TRI, LOOP, FCNA, TK8, false, false, GRID, JT0, __VA_ARGS__);                                          \
     } while (0)
     // first pass: one tile per workgroup — all tiles, or the list of live ones, whose length only the device knows: the grid
     // is cut for the expected number and a walked launch stands by for what a longer list leaves over (it leaves at once
@@ -1503,9 +1531,22 @@ extern "C" int mdh_debug_lane_stamps(unsigned long long *out, int n)
 }
 #endif
 namespace mdh { int lane_last_listed() { return lane::g_last_listed; } }
+namespace mdh { int last_grid_was_slot(); } // cell_grid.hip
+namespace mdh {
+int lane_listed_hint(int64_t N, int64_t ncell)
+{
+    int device = 0;
+    (void)hipGetDevice(&device);
+    std::lock_guard<std::mutex> lk(lane::g_stat_mu);
+    for (auto &e : lane::g_stat)
+        if (e.N == N && e.ncell == ncell && e.device == device) return ((const volatile int *)e.host)[GridStats::NBIN];
+    return -1;
+}
+} // namespace mdh
 extern "C" int mdh_debug_neighbor_plan(int *plan8)
 {
     for (int k = 0; k < 8; ++k) plan8[k] = mdh::lane::g_last_plan[k];
+    if (plan8[0] > 0 && mdh::last_grid_was_slot()) plan8[4] |= 256; // bit 8 of [4]: the last neighbor build's cell grid was a slot grid (CellGrid::slot_cap)
     mdh::lane::g_last_plan[7] = 0; // [7] = 1: the plan was made since the last query
     return MDH_OK;
 }

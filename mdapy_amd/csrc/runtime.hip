@@ -87,7 +87,7 @@ Scope::~Scope()
     // a kept block whose invariant was not restored (an error path between its first and its last kernel): zero-fill it, in
     // stream order, before the event that marks the end of this call
     for (int i = 0; i < nheld_; ++i)
-        if (held_keep_[i] == KEEP_ZERO || held_keep_[i] == KEEP_TODO)
+        if (held_keep_[i] == KEEP_ZERO || held_keep_[i] == KEEP_TODO || held_keep_[i] == KEEP_SLOT)
             (void)hipMemsetAsync(held_[i], 0, held_keep_[i] == KEEP_TODO ? std::min<size_t>(512, held_bytes_[i]) : held_bytes_[i], stream_);
     std::lock_guard<std::mutex> lk(g_mu);
     DoneEvent *done = event_acquire(stream_);
@@ -119,6 +119,13 @@ void Scope::keep_confirm(void *p)
 {
     for (int i = 0; i < nheld_; ++i)
         if (held_[i] == p) held_keep_[i] |= 0x80;
+}
+
+size_t Scope::held_bytes(const void *p) const
+{
+    for (int i = 0; i < nheld_; ++i)
+        if (held_[i] == p) return held_bytes_[i];
+    return 0;
 }
 
 void *Scope::alloc_impl(size_t bytes, int tag)

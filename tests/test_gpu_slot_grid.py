@@ -1,0 +1,273 @@
+"""-m gpu: the slot grid of the neighbour build (cell_grid.hip).  A build of spatially ordered input whose
+cells held at most eight atoms the last time bins the atoms straight into fixed cell slots: no prefix sum, no second scatter.
+Every comparison here is bitwise — rows, distances, counts and fixed-cutoff CNA labels — against the same call with
+mdh_debug_set_slot_grid(0), the compact grid; which form a call took is asserted through mdh_debug_neighbor_plan (bit 8 of [4]).
+
+The history that picks the form is kept per (N, grid); mdh_debug_set_slot_grid(2) forgets it, so that a test's first call is
+the first of its signature whatever ran before it.  Lattices of 10 and 11 cells leave a last grid cell 1.7 times as wide as the
+others (the remainder of the box); 12 cells do not.
+
+Where these cases depart from the issue that asked for them, and why.  The issue expected the 10^3-cell lattice rattled by 0.05 and
+0.20 A to hold five and six atoms per cell and to build on slots; its wide last cells hold eight (0.05 A) and nine (0.20 A, seed
+11), so by the issue's own rule the builds after the first are slot builds at 0.05 A and COMPACT ones at 0.20 A, which is what
+test_rattled asserts; test_rattled_lattice_of_twelve_cells adds the 0.20 A rattle on a box without a wide last cell, where the
+builds are slot builds.  The sheared, open-axis, unwrapped, absent-atom, exact-width and switched-off cases use 12^3 lattice cells
+instead of 10^3 for the same reason: a rattle on the 10^3 lattice would make what they are about — slot builds — depend on the seed."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from mdapy_amd import _lib, _neighbor
+from mdapy_amd.build_lattice import lattice_positions
+
+pytestmark = pytest.mark.gpu
+
+PBC = np.array([1, 1, 1], np.int32)
+ORG0 = np.zeros(3)
+A_CU = 3.615
+RC = 0.854 * A_CU
+M = 16
+
+
+@pytest.fixture(autouse=True)
+def fresh_history():
+    _lib.lib().mdh_debug_set_slot_grid(2)
+    yield
+    _lib.lib().mdh_debug_set_slot_grid(1)
+
+
+def _largest_cell(pos, box):
+    """the largest population of a cell of the rc-wide grid of an orthogonal periodic box (the last cell takes the remainder)"""
+    L = np.diag(box)
+    nc = np.maximum(np.floor(L / RC), 3).astype(int)
+    c = np.minimum(np.floor((pos % L) / RC).astype(int), nc - 1)
+    return int(np.bincount((c[:, 0] * nc[1] + c[:, 1]) * nc[2] + c[:, 2]).max())
+
+
+def _xyz(pos):
+    return tuple(np.ascontiguousarray(pos[:, k]) for k in range(3))
+
+
+def _form():
+    """True: the last neighbour build's cell grid was a slot grid (and the tile kernel made a plan for it)"""
+    plan = np.zeros(8, np.int32)
+    _lib.lib().mdh_debug_neighbor_plan(plan.ctypes.data)
+    assert plan[0] > 0, plan.tolist()
+    return bool(plan[4] & 256)
+
+
+def _build(pos, box, boundary=PBC, exact=False):
+    """(rows, distances, counts, labels) of mdh_build_neighbor_fcna at M slots (pads written), or of the exact-width driver,
+    and the grid form the call used"""
+    x, y, z = _xyz(pos)
+    n = len(x)
+    p = np.zeros(n, np.int32)
+    if exact:
+        v, d, c = _neighbor.build_neighbor_without_max_neigh(x, y, z, box, ORG0, boundary, RC, 1, pattern=p)
+    else:
+        v = np.empty((n, M), np.int32); d = np.empty((n, M)); c = np.zeros(n, np.int32)
+        _neighbor.build_neighbor_fcna(x, y, z, box, ORG0, boundary, RC, v, d, c, p, 1, fill_pads=True)
+    return (v, d, c, p), _form()
+
+
+def _compact(pos, box, boundary=PBC, exact=False):
+    prev = _lib.lib().mdh_debug_set_slot_grid(0)
+    try:
+        out, slot = _build(pos, box, boundary, exact)
+    finally:
+        _lib.lib().mdh_debug_set_slot_grid(prev)
+    assert not slot
+    return out
+
+
+def _same(tag, got, ref, ok=None):
+    for name, a, b in zip(("rows", "distances", "counts", "labels"), got, ref):
+        if ok is not None:
+            a, b = a[ok], b[ok]
+        assert a.shape == b.shape and np.array_equal(a, b), (tag, name)
+
+
+def _calls(tag, pos, box, boundary=PBC, exact=False, ok=None, forms=(False, True, True)):
+    """len(forms) calls on the same arrays, their forms asserted; all equal to the compact result, which is returned"""
+    outs = []
+    for k, want in enumerate(forms):
+        out, slot = _build(pos, box, boundary, exact)
+        assert slot == want, (tag, "call", k, "slot grid" if slot else "compact")
+        outs.append(out)
+    ref = _compact(pos, box, boundary, exact)
+    for k, out in enumerate(outs):
+        _same((tag, "call", k), out, ref, ok)
+    return ref
+
+
+def _lattice(nx, ny, nz, sigma=0.0, seed=0):
+    pos, box = lattice_positions("fcc", A_CU, nx, ny, nz)
+    if sigma:
+        pos = pos + np.random.default_rng(seed).normal(0.0, sigma, pos.shape)
+    return np.ascontiguousarray(pos), np.asarray(box, float)
+
+
+def _slot_counters():
+    out4 = (ctypes.c_int64 * 4)()
+    _lib.lib().mdh_debug_slot_grid_counters(out4)
+    return [int(v) for v in out4]
+
+
+def test_form_by_call():
+    """fcc Cu, 10^3 cells: 4 000 atoms, 11 grid cells per axis.  The first build of a signature is the compact one, the second
+    and the third bin into slots"""
+    pos, box = _lattice(10, 10, 10)
+    assert len(pos) == 4000 and int(box[0][0] // RC) == 11
+    v, d, c, p = _calls("lattice", pos, box)
+    assert (c == 12).all() and (p == 1).all()
+
+
+@pytest.mark.parametrize("sigma", [0.05, 0.20])
+def test_rattled(sigma):
+    """the same lattice rattled: cells of five and six atoms, and up to eight or nine in the wide last cells of the axes — the
+    eight-wide sorting network, full cells; where a cell holds more than eight, the builds after the one that saw it are compact"""
+    pos, box = _lattice(10, 10, 10, sigma, seed=11)
+    fits = _largest_cell(pos, box) <= 8
+    assert fits == (sigma < 0.1)  # (seed 11: 8 at 0.05 A, 9 at 0.20 A)
+    v, d, c, p = _calls(("rattled", sigma), pos, box, forms=(False, fits, fits))
+    assert c.min() < 12 if sigma > 0.1 else (p == 1).sum() > 0.9 * len(pos)
+
+
+def test_rattled_lattice_of_twelve_cells():
+    """0.20 A on a box without a wide last cell: cells of up to six atoms, slot builds"""
+    pos, box = _lattice(12, 12, 13, 0.20, seed=11)
+    assert 5 <= _largest_cell(pos, box) <= 8
+    _calls("rattled, 12 cells", pos, box)
+
+
+def test_small_shear():
+    """a periodic box sheared by 5 %: the TRI instances of the binning, the tile kernel and the mop-up"""
+    pos, box = _lattice(12, 12, 12, 0.03, seed=12)
+    sheared = box.copy()
+    sheared[1][0] = 0.05 * box[1][1]
+    pos = np.ascontiguousarray(pos @ np.linalg.inv(box) @ sheared)
+    v, d, c, p = _calls("sheared", pos, sheared)
+    assert (c == 12).sum() > 0.9 * len(pos)
+
+
+def test_open_axis_with_atoms_outside_the_box():
+    """z open; a few atoms handed in beyond both faces are clamped into the edge cells"""
+    pos, box = _lattice(12, 12, 12, 0.03, seed=13)
+    rng = np.random.default_rng(14)
+    out = rng.choice(len(pos), 6, replace=False)
+    pos[out[:3], 2] = box[2][2] + rng.random(3) * 1.5
+    pos[out[3:], 2] = -rng.random(3) * 1.5
+    v, d, c, p = _calls("open z", pos, box, boundary=np.array([1, 1, 0], np.int32))
+    assert c.min() < 12
+
+
+def _spread_and_packed():
+    """the 10^3 lattice plus twelve extra atoms, spread over twelve cells (N = 4 012), and the same with the twelve in ONE cell"""
+    lattice, box = _lattice(10, 10, 10)
+    rng = np.random.default_rng(15)
+    cells = np.array([(1 + k % 4, 2 + k // 4, 3 + k % 3) for k in range(12)], float)
+    assert len({tuple(c) for c in cells}) == 12
+    spread = np.concatenate([lattice, (cells + 0.5 + 0.2 * (rng.random((12, 3)) - 0.5)) * RC])
+    packed = spread.copy()
+    packed[-12:] = (np.array([5.5, 5.5, 5.5]) + 0.3 * (rng.random((12, 3)) - 0.5)) * RC
+    assert len(spread) == 4012
+    return spread, packed, box
+
+
+def test_overflowed_cell_under_the_thread_per_atom_kernel():
+    """the packed cell AND an atom 20 box lengths away in one call: the thread-per-atom kernel takes the whole call from a slot grid
+    with a spill list — its walk of an overflowed cell in descending id over slots and spill entries (next_id_below), which the
+    listed tiles of the test below reach only through the wave-per-atom form"""
+    L = _lib.lib()
+    spread, packed, box = _spread_and_packed()
+    far = packed.copy()
+    far[77] = far[77] + np.array([20.0, 0.0, -20.0]) * np.diag(box)
+    _calls("spread", spread, box, forms=(False, True))
+    out4 = (ctypes.c_int64 * 4)()
+    L.mdh_debug_track_counters(1)
+    try:
+        got, slot = _build(far, box)
+        L.mdh_debug_counters(out4)
+    finally:
+        L.mdh_debug_track_counters(0)
+    s = _slot_counters()
+    assert slot and int(out4[2]) == 1 and s[1] == 1 and 13 <= s[2] <= 16, (slot, list(out4), s)
+    _same("packed and far", got, _compact(far, box))
+
+
+def test_overflow_goes_to_the_spill_list_and_back_to_the_compact_grid():
+    """twelve extra atoms: spread over twelve cells they fit the slots; moved into one cell they make it hold 13 to 16 — that call
+    is still a slot build by history, its result the compact one's, and the build after it is a compact one"""
+    L = _lib.lib()
+    spread, packed, box = _spread_and_packed()
+    _calls("spread", spread, box)  # compact, slot, slot
+    got, slot = _build(packed, box)
+    assert slot  # by history
+    s = _slot_counters()
+    assert s[0] == 1 and s[1] == 1 and 13 <= s[2] <= 16 and s[3] == 8, s  # a cell of 13 ... 16: 5 ... 8 atoms on the spill list
+    after, slot_after = _build(packed, box)
+    assert not slot_after  # the overflow, and the tiles it listed, were reported
+    out4 = (ctypes.c_int64 * 4)()
+    L.mdh_debug_counters(out4)
+    assert out4[1] > 0, list(out4)  # what the previous build (the overflowed one) listed, as this build's plan read it
+    ref = _compact(packed, box)
+    _same("packed, slot build", got, ref)
+    _same("packed, compact after it", after, ref)
+    assert ref[2].max() > M  # rows inside the cluster overflow: the counts keep running
+
+
+def test_unwrapped_input():
+    """within +-3 box lengths: image codes, still the tile kernel; one atom 20 box lengths away: the thread-per-atom kernel takes
+    the whole call from the slot grid"""
+    L = _lib.lib()
+    pos, box = _lattice(12, 12, 12, 0.03, seed=16)
+    rng = np.random.default_rng(17)
+    near = pos + rng.integers(-3, 4, pos.shape) * np.diag(box)
+    far = near.copy()
+    far[1234] = pos[1234] + np.array([20.0, 0.0, -20.0]) * np.diag(box)
+    out4 = (ctypes.c_int64 * 4)()
+    L.mdh_debug_track_counters(1)
+    try:
+        _build(pos, box)  # the signature's first build
+        for tag, p, moved in (("near", near, 0), ("far", far, 1)):
+            got, slot = _build(p, box)
+            L.mdh_debug_counters(out4)
+            assert slot and int(out4[2]) == moved, (tag, slot, list(out4))
+            _same(tag, got, _compact(p, box))
+    finally:
+        L.mdh_debug_track_counters(0)
+
+
+def test_absent_atoms():
+    """x = NaN: no cell, no slot, no row, in nobody's row"""
+    pos, box = _lattice(12, 12, 12, 0.03, seed=18)
+    rng = np.random.default_rng(19)
+    gone = rng.random(len(pos)) < 0.01
+    gone[1000:1003] = True; gone[64 * 20:64 * 21] = True
+    pos[gone, 0] = np.nan
+    ok = ~gone
+    v, d, c, p = _calls("absent", pos, box, ok=ok)
+    assert not np.isin(np.nonzero(gone)[0], v[ok]).any() and c[ok].min() < 12
+
+
+def test_exact_width_driver_twice():
+    """max_neigh=None: the counting pass and the build share one grid"""
+    pos, box = _lattice(12, 12, 12, 0.05, seed=20)
+    v, d, c, p = _calls("exact", pos, box, exact=True, forms=(False, True))
+    assert v.shape[1] == c.max()
+
+
+def test_switched_off():
+    """mdh_debug_set_slot_grid(0): every call is a compact build"""
+    pos, box = _lattice(12, 12, 12, 0.05, seed=21)
+    prev = _lib.lib().mdh_debug_set_slot_grid(0)
+    try:
+        outs = [_build(pos, box) for _ in range(3)]
+    finally:
+        _lib.lib().mdh_debug_set_slot_grid(prev)
+    assert not any(slot for _, slot in outs)
+    got, slot = _build(pos, box)
+    assert slot  # (the history was kept all along)
+    for out, _ in outs:
+        _same("off", out, got)
