@@ -495,6 +495,34 @@ int mdh_knn_keyed_rows(const double *x, const double *y, const double *z, int64_
 /* slots per atom a search for k neighbours wants in rows_io (0: the rows path does not serve this k) */
 int mdh_knn_rows_width(int k);
 
+/* ---- _fast_knn.Tree: nearest reference site, site occupancy (Wigner-Seitz) ---- */
+/* replaces _fast_knn.Tree                                   src/fast_knn.cpp:924-972
+ * The nearest of N reference sites for every one of Q query points: the sites and the queries wrapped as in mdh_knn, images
+ * +-nimages per periodic axis (nimages = 200 / clamp(N, 50, 200), >= 2 in a triclinic box), d2 = |a - (q_wrapped - shift)|^2 in
+ * f64, k = 1 and NO self-exclusion.  EXACT ties in d2 go to the lowest site index.  A query with a non-finite coordinate (after
+ * the map), or N == 0, gets index -1.
+ *
+ * The site grid belongs to the CALLER: mdh_ws_build writes it into site_records (N x 4 f64: the cell-sorted wrapped sites, the
+ * original site index as an i32 in the first four bytes of the fourth slot) and cell_start (ncell + 1 i32, ncell from
+ * mdh_ws_grid_cells), and every later mdh_ws_query is handed the same two buffers with the same N and box; no state lives in the
+ * library.  The grid's shape is a function of (N, box) alone.  site_records is read in 16-byte requests: in device space it must be
+ * 16-byte aligned (MDH_ERR_ARG otherwise).  Range: the result is the exact nearest site for queries within 1e4 box lengths of the
+ * box along periodic axes; farther out the reference's wrap p -= s L loses ~1e-16 |p|, which approaches the 1e-9 cell widths the
+ * ring walk's stop test allows for, and the site returned is nearest only to within that rounding. */
+int mdh_ws_grid_cells(int64_t N, const double *box9_host, const double *origin3_host, const int *boundary3_host, int64_t *ncell_host);
+int mdh_ws_build(const double *x, const double *y, const double *z, int64_t N, const double *box9_host, const double *origin3_host,
+                 const int *boundary3_host, double *site_records, int *cell_start, int space, void *stream);
+/* indices (Q) i32; map9_host (9 f64, row-major, host; NULL: none) maps each query first, as in mdh_strain_pack */
+int mdh_ws_query(const double *site_records, const int *cell_start, int64_t N, const double *box9_host, const double *origin3_host,
+                 const int *boundary3_host, const double *qx, const double *qy, const double *qz, int64_t Q, const double *map9_host,
+                 int *indices, int space, void *stream);
+/* from indices (Q): site_occupancy (N) i32 = atoms per site; atom_occupancy (Q) i32 = site_occupancy[indices[i]];
+ * atom_site_type (Q) i32 = site_type[indices[i]] (both NULL: not wanted); counts2_host (2 i32, host) = the number of sites with
+ * occupancy 0 and the sum of max(occupancy - 1, 0).  An index outside [0, N) is counted nowhere: occupancy 0, type -1.
+ * Synchronises the stream (the two counts are read back). */
+int mdh_ws_occupancy(const int *indices, int64_t Q, int64_t N, const int *site_type, int *site_occupancy, int *atom_occupancy,
+                     int *atom_site_type, int *counts2_host, int space, void *stream);
+
 /* ---- _repeat_cell ----------------------------------------------------- */
 /* replaces _repeat_cell.repeat_cell                        src/repeat_cell.cpp:19-61; new_pos flat (n_old*nx*ny*nz*3) */
 int mdh_repeat_cell(double *new_pos, const double *old_box9_host, const double *old_pos, int64_t n_old, int nx,

@@ -17,6 +17,7 @@ from .radial_distribution_function import RadialDistributionFunction
 from .warren_cowley_parameter import WarrenCowleyParameter
 from .atomic_strain import AtomicStrain
 from .chill_plus import ChillPlus
+from .wigner_seitz_defect import WignerSeitzAnalysis
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -24,6 +25,6 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "ChillPlus",
+    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

@@ -106,6 +106,10 @@ _SIGNATURES = {
     "mdh_knn_keyed": [vp, vp, vp, i64, vp, vp, vp, cint, vp, vp, vp, cint, vp],
     "mdh_knn_keyed_rows": [vp, vp, vp, i64, vp, vp, vp, cint, vp, vp, vp, vp, vp, cint, vp, cint, vp],
     "mdh_knn_rows_width": [cint],
+    "mdh_ws_grid_cells": [i64, vp, vp, vp, vp],
+    "mdh_ws_build": [vp, vp, vp, i64, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_ws_query": [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, cint, vp],
+    "mdh_ws_occupancy": [vp, i64, i64, vp, vp, vp, vp, vp, cint, vp],
     "mdh_repeat_cell": [vp, vp, vp, i64, cint, cint, cint, cint, vp],
     "mdh_ptm": [C.c_char_p, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, dbl, vp, cint, vp, cint, cint, vp],
     "mdh_ptm_flags": [C.c_char_p],

@@ -20,6 +20,7 @@
 // list in registers; the queries it cannot prove go to k_knn through a to-do list.
 #include "common.hpp"
 #include "grid.hpp"
+#include "knn_geom.hpp"
 #include <cstring>
 #include <type_traits>
 #include <cstdlib>
@@ -27,12 +28,6 @@
 namespace mdh {
 
 int g_knn_variant = 0; // 0 = near kernel + general kernel, 1 = general kernel only (tests, A/B), 3 = counting kernel first (measuring variant)
-
-struct KnnGeom {
-    int nim[3];    // images per axis (0 on open axes)
-    double wmin;   // smallest perpendicular cell width
-    int rmax;      // ring index after which every (cell, image) has been visited
-};
 
 template <bool TRI>
 __global__ __launch_bounds__(256) void k_knn_wrap(const double *__restrict__ x, const double *__restrict__ y,
@@ -44,26 +39,9 @@ __global__ __launch_bounds__(256) void k_knn_wrap(const double *__restrict__ x, 
     if (i >= N)
         return;
     double px = x[i], py = y[i], pz = z[i];
-    if (TRI) {
-        const double r0 = px * b.hi[0] + py * b.hi[3] + pz * b.hi[6];
-        const double r1 = px * b.hi[1] + py * b.hi[4] + pz * b.hi[7];
-        const double r2 = px * b.hi[2] + py * b.hi[5] + pz * b.hi[8];
-        const double r[3] = {r0, r1, r2};
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            if (b.pbc[d]) {
-                const double s = floor(r[d]);
-                if (s != 0.0) { px -= s * b.h[d * 3 + 0]; py -= s * b.h[d * 3 + 1]; pz -= s * b.h[d * 3 + 2]; }
-            }
-    } else {
-        if (b.pbc[0]) { const double s = floor((px - b.o[0]) * (1.0 / b.h[0])); if (s != 0.0) px -= s * b.h[0]; }
-        if (b.pbc[1]) { const double s = floor((py - b.o[1]) * (1.0 / b.h[4])); if (s != 0.0) py -= s * b.h[4]; }
-        if (b.pbc[2]) { const double s = floor((pz - b.o[2]) * (1.0 / b.h[8])); if (s != 0.0) pz -= s * b.h[8]; }
-    }
+    knn_wrap_point<TRI>(b, px, py, pz);
     wx[i] = px; wy[i] = py; wz[i] = pz;
 }
-
-__device__ __forceinline__ int floordiv(int a, int n) { int q = a / n; return (a % n < 0) ? q - 1 : q; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The k nearest from the rows of a CUTOFF build (round 6).  For a system of even density — a crystal, a glass, a liquid: what the
@@ -85,22 +63,7 @@ __global__ __launch_bounds__(256) void k_knn_wrap4(const double *__restrict__ x,
     if (i >= N)
         return;
     double px = x[i], py = y[i], pz = z[i]; // (k_knn_wrap)
-    if (TRI) {
-        const double r0 = px * b.hi[0] + py * b.hi[3] + pz * b.hi[6];
-        const double r1 = px * b.hi[1] + py * b.hi[4] + pz * b.hi[7];
-        const double r2 = px * b.hi[2] + py * b.hi[5] + pz * b.hi[8];
-        const double r[3] = {r0, r1, r2};
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            if (b.pbc[d]) {
-                const double s = floor(r[d]);
-                if (s != 0.0) { px -= s * b.h[d * 3 + 0]; py -= s * b.h[d * 3 + 1]; pz -= s * b.h[d * 3 + 2]; }
-            }
-    } else {
-        if (b.pbc[0]) { const double s = floor((px - b.o[0]) * (1.0 / b.h[0])); if (s != 0.0) px -= s * b.h[0]; }
-        if (b.pbc[1]) { const double s = floor((py - b.o[1]) * (1.0 / b.h[4])); if (s != 0.0) py -= s * b.h[4]; }
-        if (b.pbc[2]) { const double s = floor((pz - b.o[2]) * (1.0 / b.h[8])); if (s != 0.0) pz -= s * b.h[8]; }
-    }
+    knn_wrap_point<TRI>(b, px, py, pz);
     w[i] = Pos4{px, py, pz, 0.0};
 }
 
@@ -736,7 +699,7 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
     const double *dx = sc.stage_in(x, (size_t)N, space), *dy = sc.stage_in(y, (size_t)N, space), *dz = sc.stage_in(z, (size_t)N, space);
     int *di = sc.stage(indices, (size_t)(N * k), space, false, true);
     double *dd = sc.stage(distances, (size_t)(N * k), space, false, true);
-    const double vol = std::fabs(b.tri ? (b.h[0] * (b.h[4] * b.h[8] - b.h[5] * b.h[7]) - b.h[1] * (b.h[3] * b.h[8] - b.h[5] * b.h[6]) + b.h[2] * (b.h[3] * b.h[7] - b.h[4] * b.h[6])) : b.h[0] * b.h[4] * b.h[8]);
+    const double vol = knn_box_volume(b);
     const int64_t *dkey = key ? sc.stage_in(key, (size_t)N, space) : nullptr;
     // ---- the k nearest from the rows of a cutoff build (k_knn_rows): large systems in boxes of at least 7.5 radii per periodic vector
     // (the tile kernel's domain, and the nearest image of a listed neighbour is then beyond doubt); MDH_KNN_ROWS=0 or variant != 0: off
@@ -834,50 +797,13 @@ extern "C" int mdh_knn_keyed_rows(const double *x, const double *y, const double
 
     // images per periodic axis (fast_knn.cpp:806-816)
     KnnGeom kg;
-    int nim = 1;
-    if (b.anypbc) {
-        int64_t cl = N < 50 ? 50 : (N > 200 ? 200 : N);
-        nim = (int)(200 / cl);
-        if (nim < 1) nim = 1;
-        if (nim < 2 && b.tri) nim = 2;
-    }
-    for (int d = 0; d < 3; ++d) kg.nim[d] = b.pbc[d] ? nim : 0;
+    knn_images(b, N, kg);
 
     // grid: aim at ~k/3+1 atoms per cell so that ring 1 usually holds the k nearest
     DBox bg = b;
     if (b.tri) bg.o[0] = bg.o[1] = bg.o[2] = 0.0; // the triclinic wrap above is anchored at 0, not at the origin
     CellGrid cg;
-    const double per_cell = (double)k / 3.0 + 1.0;
-    double wtarget = std::cbrt(vol * per_cell / (double)N);
-    if (!(wtarget > 0) || !std::isfinite(wtarget)) wtarget = 1.0;
-    double tot = 1.0;
-    kg.wmin = __builtin_huge_val();
-    kg.rmax = 0;
-    for (int d = 0; d < 3; ++d) {
-        const double th = std::fabs(b.thick[d]);
-        double f = std::floor(th / wtarget);
-        int n = (f < 1.0 || !(f == f)) ? 1 : (f > 1024.0 ? 1024 : (int)f);
-        cg.g.nc[d] = n;
-        tot *= n;
-    }
-    // keep the grid below ~4 cells per atom (sparse / slab-like systems)
-    while (tot > 4.0 * (double)N + 64.0) {
-        int dmax = 0;
-        for (int d = 1; d < 3; ++d) if (cg.g.nc[d] > cg.g.nc[dmax]) dmax = d;
-        if (cg.g.nc[dmax] <= 1) break;
-        tot /= cg.g.nc[dmax];
-        cg.g.nc[dmax] = (cg.g.nc[dmax] + 1) / 2;
-        tot *= cg.g.nc[dmax];
-    }
-    for (int d = 0; d < 3; ++d) {
-        const double w = std::fabs(b.thick[d]) / cg.g.nc[d];
-        if (w < kg.wmin) kg.wmin = w;
-        const int r = b.pbc[d] ? (kg.nim[d] + 1) * cg.g.nc[d] : cg.g.nc[d] - 1;
-        if (r > kg.rmax) kg.rmax = r;
-    }
-    cg.g.ncell = (int64_t)cg.g.nc[0] * cg.g.nc[1] * cg.g.nc[2];
-    cg.g.rc_inv = 0.0;
-    cg.g.mode = 1;
+    knn_size_grid(b, N, (double)k / 3.0 + 1.0, cg.g, kg);
     MDH_TRY(build_cell_grid(sc, wx, wy, wz, N, bg, GridRequest{}, cg)); // (positions wrapped above; sorted coordinate arrays, cells in any order)
     int *label = nullptr, *unlabel = nullptr;
     if (key) {
