@@ -1,6 +1,6 @@
 """Drop-in for the reference's ``mdapy._neighbor`` nanobind module
 (src/neighbor.cpp:841-859): same function names, argument order and
-caller-allocated outputs, executed by the HIP kernels in csrc/neighbor.hip (the cell grid under them: csrc/cell_grid.hip).
+caller-allocated outputs, executed by the HIP kernels in csrc/neighbor.hip and csrc/rows.hip (the cell grid under them: csrc/cell_grid.hip).
 Arrays may be numpy (host; staged by the library) or HBM resident
 (:class:`mdapy_amd.devarray.HArray`, frame columns, torch ROCm tensors)."""
 import numpy as np

@@ -8,7 +8,7 @@ larger than ``face_threshold`` and the metal / carbon contacts are thinned by th
 
 Where the work is done: the cells — :class:`mdapy_amd.voronoi.Container` (csrc/voronoi.hip); filling a grain —
 ``transform_and_filter`` (csrc/polycrystal.hip: rotate, translate, half-space test against the face planes in LDS,
-order-preserving compaction); contacts — ``filter_overlap_atom[_with_grain]`` (csrc/neighbor.hip, csrc/polycrystal.hip;
+order-preserving compaction); contacts — ``filter_overlap_atom[_with_grain]`` (csrc/rows.hip, csrc/polycrystal.hip;
 the reference's order-dependent sweep in its serial order); wrapping — ``System.wrap_pos``.  The random draws (seed
 positions, Euler angles) are made in the reference's order from the same generator, so a given ``randomseed`` gives the
 same grains."""

@@ -271,6 +271,12 @@ __device__ __forceinline__ int wave_max(int v)
     for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
     return v;
 }
+// *out = max(*out, m), m being the wave's value (wave_max): lane 0 reads the word first, a plain device-scope load — a single word
+// takes ~90 atomics per microsecond, so 200 000 waves must not all queue on it; almost every wave finds the maximum already there
+__device__ __forceinline__ void raise_max(int *out, int m)
+{
+    if ((threadIdx.x & 63) == 0 && m > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, m);
+}
 
 // An index taken from a caller's list, made safe to dereference: an entry outside [0, n) (a pad of a k-nearest list in a
 // system of fewer than k+1 atoms, a list that belongs to another system) reads atom `fallback` instead of faulting the

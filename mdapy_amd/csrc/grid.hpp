@@ -76,15 +76,11 @@ struct CellGrid {
     unsigned big_gen = 0;
     int *big_sink = nullptr;
 };
-// atoms a cell of a slot grid holds in place (two planes of four ids, slot_pos); MDH_SLOT_CAP=4 is the measuring build of profiles/slot_grid.md
-#ifndef MDH_SLOT_CAP
-#define MDH_SLOT_CAP 8
-#endif
-constexpr int SLOT_CAP = MDH_SLOT_CAP;
-static_assert(SLOT_CAP == 4 || SLOT_CAP == 8, "a cell's slots are one or two 16-byte loads");
+// atoms a cell of a slot grid holds in place (two planes of four ids, slot_pos)
+constexpr int SLOT_CAP = 8;
 // position in CellGrid::order of slot k (< SLOT_CAP) of cell c; hi: CellGrid::slot_hi
 __host__ __device__ __forceinline__ int64_t slot_pos(int64_t c, int k, int64_t hi) { return c * 4 + k + (k >= 4 ? hi - 4 : 0); }
-// the second plane and the spill list of a slot grid, as the thread-per-atom kernels see them (neighbor.hip)
+// the second plane and the spill list of a slot grid, as the thread-per-atom kernels see them (CellView below)
 struct SlotSpill { const int2 *list = nullptr; const unsigned *n = nullptr; int64_t hi = 0; };
 // a cell-sorted atom, from either representation
 struct SortedView {
@@ -97,6 +93,24 @@ struct SortedView {
         if (pk) { const CellGrid::Packed r = pk[q]; x = r.x; y = r.y; z = r.z; id = r.id; }
         else if (indirect) { id = order[q]; x = xs[id]; y = ys[id]; z = zs[id]; }
         else { x = xs[q]; y = ys[q]; z = zs[q]; id = order[q]; }
+    }
+    // four of them, every load of the four issued before the first is used: the form is looked at once, not per atom
+    __device__ __forceinline__ void get4(const int64_t (&q)[4], double (&x)[4], double (&y)[4], double (&z)[4], int (&id)[4]) const
+    {
+        if (pk) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const CellGrid::Packed r = pk[q[u]]; x[u] = r.x; y[u] = r.y; z[u] = r.z; id[u] = r.id; }
+            return;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) id[u] = order[q[u]];
+        if (indirect) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { x[u] = xs[id[u]]; y[u] = ys[id[u]]; z[u] = zs[id[u]]; }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { x[u] = xs[q[u]]; y[u] = ys[q[u]]; z[u] = zs[q[u]]; }
+        }
     }
     __device__ __forceinline__ int id_of(int64_t q) const { return pk ? pk[q].id : order[q]; }
 };
@@ -235,6 +249,113 @@ __device__ __forceinline__ void cell_coords(const DBox &b, const Grid &g, double
     c1 = (int)f1;
     c2 = (int)f2;
 }
+
+// The cell grid as the thread-per-atom and wave-per-atom kernels of neighbor.hip walk it, in either of its two forms.
+//   Compact (SLOT = false): position p of the cell order names an atom, a cell is the range [cell_start[c], cell_start[c + 1]) of it,
+//     and the three cells of a z-run that does not cross the box's face are ONE range.
+//   Slot grid (SLOT = true, CellGrid::slot_cap): cell_start[c] is the cell's COUNT, its first SLOT_CAP ids sit in descending order in
+//     the cell's slots of `order` (slot_pos), the cells are walked one by one, a centre is named by its id (p = id: the atoms are the
+//     caller's arrays), and a cell whose count ran past SLOT_CAP has the rest of its atoms on the spill list.
+// The candidates of a centre — the atoms of the 27 cells around it in the reference's order (neighbor.cpp:147-151), each cell's by
+// descending id — come as a sequence of pieces (for_each_piece), a piece being one of
+//   a run:              n consecutive positions of the cell order from `at` (compact);
+//   a cell's slots:     the n <= SLOT_CAP slot positions of cell `at` (slot grid);
+//   an overflowed cell: cell `at` with n > SLOT_CAP atoms, handed out one by one in descending id by next_id_below (slot grid).
+// Candidate k of a piece of the first two kinds is read at pos(piece, k).
+struct CellPiece { int64_t at; int n; };
+template <bool SLOT>
+struct CellView {
+    SortedView sv;
+    const int *__restrict__ cell_start;
+    SlotSpill sp; // (a compact grid has none: never read)
+
+    // centres are numbered 0 ... centres() - 1: the atoms the grid holds (cell_start[ncell]: N, or fewer after a windowed build that
+    // dropped atoms outside its window — the records behind them were never written); a slot grid takes them by id from the caller's
+    // arrays — its atoms are in a spatial order already
+    __device__ __forceinline__ int64_t centres(int64_t N, const Grid &g) const { return SLOT ? N : min(N, (int64_t)cell_start[g.ncell]); }
+    // centre p: its raw position and its id; -1: an absent atom (slot grid, x = NaN), which has no cell and gets no row
+    __device__ __forceinline__ int centre(int64_t p, double &x, double &y, double &z) const
+    {
+        int id;
+        if (SLOT) { id = (int)p; x = sv.xs[p]; y = sv.ys[p]; z = sv.zs[p]; return x == x ? id : -1; }
+        sv.get(p, x, y, z, id);
+        return id;
+    }
+    // the pieces of the centre in cell (c0, c1, c2), in candidate order: f(piece) for each
+    template <class F>
+    __device__ __forceinline__ void for_each_piece(const Grid &g, int c0, int c1, int c2, F &&f) const
+    {
+        const bool zrun = !SLOT && c2 >= 1 && c2 + 1 < g.nc[2]; // the three z-cells are one contiguous run
+        for (int a = c0 - 1; a <= c0 + 1; ++a) {                // neighbor.cpp:147-151
+            const int ca = pmod(a, g.nc[0]);
+            for (int bb = c1 - 1; bb <= c1 + 1; ++bb) {
+                const int64_t base = ((int64_t)ca * g.nc[1] + pmod(bb, g.nc[1])) * g.nc[2];
+                for (int seg = 0; seg < (zrun ? 1 : 3); ++seg) {
+                    const int64_t cell = base + (zrun ? c2 - 1 : pmod(c2 - 1 + seg, g.nc[2]));
+                    if (SLOT) {
+                        f(CellPiece{cell, cell_start[cell]});
+                    } else {
+                        const int s = cell_start[cell];
+                        f(CellPiece{s, cell_start[cell + (zrun ? 3 : 1)] - s});
+                    }
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ bool overflowed(const CellPiece &pc) const { return SLOT && pc.n > SLOT_CAP; }
+    __device__ __forceinline__ int64_t pos(const CellPiece &pc, int k) const { return SLOT ? slot_pos(pc.at, k, sp.hi) : pc.at + k; }
+    // the largest id below `prev` among the atoms of an overflowed cell — its slots and its entries of the spill list — or -1: a
+    // selection walk, one pass over the (short) list per candidate; the rare path, and the next build of the signature is a compact one
+    __device__ __forceinline__ int next_id_below(int64_t cell, int prev) const
+    {
+        int best = -1;
+        for (int u = 0; u < SLOT_CAP; ++u) {
+            const int v = sv.order[slot_pos(cell, u, sp.hi)];
+            if (v < prev && v > best) best = v;
+        }
+        const unsigned ns = *sp.n;
+        for (unsigned w = 0; w < ns; ++w) {
+            const int2 e = sp.list[w];
+            if ((int64_t)e.x == cell && e.y < prev && e.y > best) best = e.y;
+        }
+        return best;
+    }
+    // The centres of the cells [z0, z1) of the column that starts at cell `col`, numbered 0, 1, ... as they come: f(p) for number
+    // `first` and every `step`-th behind it.  Compact: the z-run of a column is contiguous in the cell order; slot grid: cell by
+    // cell, the slots and then the cell's entries of the spill list.
+    template <class F>
+    __device__ __forceinline__ void for_each_column_centre(int64_t col, int z0, int z1, int first, int step, F &&f) const
+    {
+        if (SLOT) {
+            int seen = 0;
+            for (int cz = z0; cz < z1; ++cz) {
+                const int n = cell_start[col + cz];
+                for (int k = 0; k < n; ++k, ++seen) {
+                    if (seen % step != first)
+                        continue;
+                    const int id = cell_atom(col + cz, k);
+                    if (id >= 0) f((int64_t)id);
+                }
+            }
+        } else {
+            const int e = cell_start[col + z1];
+            for (int p = cell_start[col + z0] + first; p < e; p += step) f((int64_t)p);
+        }
+    }
+    // the k-th atom of a cell of a slot grid, in any fixed order (every atom of the cell once); -1: none
+    __device__ __forceinline__ int cell_atom(int64_t cell, int k) const
+    {
+        if (k < SLOT_CAP)
+            return sv.order[slot_pos(cell, k, sp.hi)];
+        k -= SLOT_CAP;
+        const unsigned ns = *sp.n;
+        for (unsigned w = 0; w < ns; ++w) {
+            const int2 e = sp.list[w];
+            if ((int64_t)e.x == cell && k-- == 0) return e.y;
+        }
+        return -1;
+    }
+};
 
 // fills cg.g for the cutoff neighbor search: nc = max(floor(thickness/rc), 3) (neighbor.cpp:203-206)
 int neighbor_grid_dims(const DBox &b, double rc, Grid &g);

@@ -1091,14 +1091,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
             break;
         if (jt + (int)(gridDim.x >> 3) < per) lds_barrier(); // LDS is reused by the next tile
     } // tiles of this workgroup
-    if (COUNT) {
-        int m = vmax;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d, 64));
-        // one word takes ~90 atomics per microsecond: 200 000 waves must not all queue on it.  Almost every wave finds the
-        // maximum already there (a plain device-scope read), the few that raise it use the atomic.
-        if (lane == 0 && m > __hip_atomic_load(max_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(max_count, m);
-    }
+    if (COUNT) raise_max(max_count, wave_max(vmax));
 }
 
 // tiles with at least one centre atom: flag (one thread per tile), then an order-preserving compaction

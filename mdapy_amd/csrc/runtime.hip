@@ -384,6 +384,7 @@ namespace mdh {
 void warm_prof(hipStream_t st);
 void warm_cell_grid(hipStream_t st);
 void warm_neighbor(hipStream_t st);
+void warm_rows(hipStream_t st);
 void warm_neighbor_tiled(hipStream_t st);
 void warm_neighbor_lane(hipStream_t st);
 void warm_cna(hipStream_t st);
@@ -507,6 +508,7 @@ int mdh_warm(void)
     mdh::warm_prof(nullptr);
     mdh::warm_cell_grid(nullptr);
     mdh::warm_neighbor(nullptr);
+    mdh::warm_rows(nullptr);
     mdh::warm_neighbor_tiled(nullptr);
     mdh::warm_neighbor_lane(nullptr);
     mdh::warm_cna(nullptr);

@@ -18,7 +18,7 @@
 
 namespace mdh {
 
-int sort_rows_any_tie_order(int *dv, double *dd, int64_t N, int64_t M, void *stream); // neighbor.hip
+int sort_rows_any_tie_order(int *dv, double *dd, int64_t N, int64_t M, void *stream); // rows.hip
 static int g_listed_passes = 0; // passes of the last call that went over the atoms with open cells only (mdh_debug_counters out4[3])
 int voro_listed_passes() { return g_listed_passes; }
 static constexpr int VORO_MAXC = 250;  // neighbours one cell may consider
