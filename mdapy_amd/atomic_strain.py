@@ -49,9 +49,8 @@ class AtomicStrain:
     def _reference(self):
         """(rows, counts, box, position columns, permutation or None) the strain is computed over"""
         ref = self.ref
-        mirror, state = ref.__dict__.get("_mirror"), ref.__dict__.get("_twin_state")
-        if mirror is not None and state is not None and state[1] is not None and ref.__dict__.get("verlet_list") is mirror["rows"] \
-                and "verlet_list" in state[1].__dict__:
+        state = ref.__dict__.get("_twin_state")
+        if state is not None and state[1] is not None and ref._mirrors_twin() and "verlet_list" in state[1].__dict__:
             twin = state[1]  # the list lives on the cell-sorted twin; ref.verlet_list is its untranslated mirror
             return twin.verlet_list, twin.neighbor_number, ref.box, policy.positions(twin.data), twin._perm
         cell, frame = ref._get_compute_view()

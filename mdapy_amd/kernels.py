@@ -7,7 +7,8 @@ CPU test-suite swap the shims for the oracle without a backend switch inside the
 from . import _aja as aja
 from . import _atomtemp as atomtemp
 # (not in NAMES: the CPU suite's oracle backend asserts an adapter for every name there, and the oracle has no bond analysis;
-# its tests install a restatement of their own as kernels.bond_analysis)
+# its tests install a restatement of their own as kernels.bond_analysis — one by one, or all of them with
+# tests/_oracle_backend.py's install_consumers, as the randomised sweeps do)
 from . import _bond_analysis as bond_analysis
 # (not in NAMES either: the oracle has no CHILL+; its tests install a restatement as kernels.chill_plus)
 from . import _chill_plus as chill_plus

@@ -302,15 +302,23 @@ class System:
         self.__dict__.pop("_twin_cols", None)
         return twin
 
+    def _mirrors_twin(self):
+        """whether the list this system remembers is the twin's list, translated, rows in the twin's order.  Sorting the front
+        columns of the mirror in place would leave the same object with other rows than the twin's — and sums, and an ADF whose
+        two ranges differ, depend on the order of a row.  ``_sort_front`` therefore sorts the twin's rows and mirrors them again;
+        were the two ever out of step all the same, the analyses run on this system itself (its list is complete)"""
+        mirror, mine = self.__dict__.get("_mirror"), self.__dict__.get("verlet_list")
+        return mirror is not None and mine is mirror["rows"] \
+            and self.__dict__.get("_sorted_columns", (None, 0)) == (id(mine), mirror["state"][3])
+
     def _twin_for(self, name, args, kwargs):
         """the twin if method ``name`` may run on it with these arguments"""
         twin = self._spatial()
         if twin is None:
             return None
         # the list this system remembers must be the twin's (translated), or neither has one
-        mirror = self.__dict__.get("_mirror")
         mine = self.__dict__.get("verlet_list")
-        if mine is not None and (mirror is None or mirror["rows"] is not mine):
+        if mine is not None and not self._mirrors_twin():
             return None
         if mine is None and "verlet_list" in twin.__dict__:
             twin._forget(_LIST)
@@ -561,6 +569,14 @@ class System:
         k-nearest search, or an earlier call) is not touched again"""
         which, done = self.__dict__.get("_sorted_columns", (None, 0))
         if which != id(self.verlet_list) or done < k:
+            state = self.__dict__.get("_twin_state")
+            if state is not None and state[1] is not None and self._mirrors_twin() and "verlet_list" in state[1].__dict__:
+                # the list is the twin's, translated: sort the twin's rows and mirror them again, so that the two stay in step and
+                # later analyses keep running on the twin (the selection looks at distances and slots, not at what the entries
+                # are called: the twin's sorted rows, translated, are this system's rows, sorted)
+                state[1]._sort_front(k)
+                self._mirror_lists(state[1])
+                return
             tool.sort_neighbor(self.verlet_list, self.distance_list, self.neighbor_number, k)
             self._sorted_columns = (id(self.verlet_list), k)
 

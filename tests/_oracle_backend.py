@@ -228,3 +228,20 @@ def install(monkeypatch):
     assert set(table) == set(K.NAMES), "an adapter per shim module"
     for name, adapter in table.items():
         monkeypatch.setattr(K, name, adapter)
+
+
+def install_consumers(monkeypatch):
+    """after ``install``: the numpy restatements of the analyses the oracle does not have (tests/_bond_ref.py, _chill_ref.py,
+    _strain_ref.py, _ws_ref.py) as the shims that stay out of ``kernels.NAMES``, and as the nearest-site members of
+    ``kernels.fast_knn`` — what the host tests of those features install one by one"""
+    import _bond_ref
+    import _chill_ref
+    import _strain_ref
+    import _ws_ref
+    import mdapy_amd.kernels as K
+
+    monkeypatch.setattr(K, "bond_analysis", _bond_ref)
+    monkeypatch.setattr(K, "chill_plus", _chill_ref)
+    monkeypatch.setattr(K, "strain", _strain_ref)
+    monkeypatch.setattr(K.fast_knn, "Tree", _ws_ref.Tree, raising=False)
+    monkeypatch.setattr(K.fast_knn, "cal_site_occupancy", _ws_ref.cal_site_occupancy, raising=False)

@@ -197,3 +197,27 @@ def test_water_fixtures(restated, tmp_path):
     adf = s.cal_angular_distribution_function({k: [0, 2.0, 0, 2.0] for k in WATER_ADF}, int(want["bins"]))
     for row, name in enumerate(WATER_ADF.values()):
         assert np.array_equal(adf.bond_angle_distribution[row], want[f"adf_{name.replace('-', '_')}"].astype(np.int64)), name
+
+
+def test_adf_after_an_in_place_sort_of_the_mirrored_list(restated):
+    """found by ``FUZZ_TWIN=1 python tests/fuzz_system.py`` at seed 60024 (rdf_long, ..., ids, adf): an analysis that does not run
+    on the cell-sorted twin sorts the front columns of the system's list in place — the list that mirrors the twin's — and the next
+    ADF ran on the twin's rows, still in their old order.  A pattern with one element for both neighbours and two different
+    ranges depends on the order of a row: the sort goes through the twin now, and a mirror that is out of step keeps the twin out"""
+    data, box = _glass(4, seed=3)
+    rc_dict = {"Cu-Cu-Cu": [0.0, 2.9, 2.0, 4.2], "Zr-Cu-Cu": [1.0, 4.2, 0.0, 3.1]}
+    got = {}
+    for mode in ("0", "1"):
+        s = mp.System(data=dict(data), box=box)
+        s._sort_mode = mode
+        s.build_neighbor(4.2)
+        assert (s._spatial() is not None) == (mode == "1")
+        s.cal_identify_diamond_structure()  # the four nearest to the front, in place
+        assert s._sorted_columns[1] >= 4
+        if mode == "1":  # the twin's rows were sorted with the mirror: the two are in step and the ADF runs on the twin
+            twin = s._spatial()
+            assert s._mirrors_twin() and twin._sorted_columns[1] >= 4 and s._twin_for("cal_angular_distribution_function", (rc_dict, 37), {}) is twin
+        got[mode] = s.cal_angular_distribution_function(rc_dict, 37).bond_angle_distribution
+        want = _direct_adf(s, rc_dict, 37)
+        assert np.array_equal(got[mode], want)
+    assert got["0"].sum() > 1000 and np.array_equal(got["0"], got["1"])
