@@ -523,6 +523,33 @@ int mdh_ws_query(const double *site_records, const int *cell_start, int64_t N, c
 int mdh_ws_occupancy(const int *indices, int64_t Q, int64_t N, const int *site_type, int *site_occupancy, int *atom_occupancy,
                      int *atom_site_type, int *counts2_host, int space, void *stream);
 
+/* ---- _lindemann ------------------------------------------------------- */
+/* The Lindemann index of a trajectory.  pos (F, N, 3) f64, C-contiguous, UNWRAPPED positions of F >= 1 frames of N >= 2 atoms;
+ * r = sqrt(dx*dx + dy*dy + dz*dz), dx = pos[f,i] - pos[f,j], for every pair and frame.  Every per-pair operation is the
+ * reference's, in its order, in IEEE binary64: the pair tables carry the reference's bits.  Sums of pair terms are taken in a
+ * fixed order of the library's own (no floating-point atomics: the same input gives the same bits on every run) and divided once.
+ * No N x N storage unless the caller passes the tables.  F < 1, N < 2 or pos == NULL return MDH_ERR_ARG (the reference yields NaN
+ * or an IndexError there), as do N > 1 048 576 and F > 2^30.
+ *
+ * replaces _lindemann.compute_global                        src/lindemann.cpp:20-74
+ * Per pair i < j: S1 = sum over the frames, in order, of r, S2 = of r * r (the square of the rounded r); its term is
+ * sqrt(S2 / F - (S1 / F) * (S1 / F)) / (S1 / F) where that difference is > 0, else none.  *result_host (one f64, host memory) =
+ * the sum of the terms / (N (N - 1) / 2).  pair_sum / pair_sumsq (N x N f64, each may be NULL: not wanted): the strict upper
+ * triangle receives S1 / S2, the rest is left as it was.  Synchronises the stream. */
+int mdh_lindemann_global(const double *pos, int64_t F, int64_t N, double *pair_sum, double *pair_sumsq, double *result_host,
+                         int space, void *stream);
+/* replaces _lindemann.compute_all                           src/lindemann.cpp:85-146
+ * Per pair and frame f the Welford update delta = r - mean; mean += delta / (f + 1); var += delta * (r - mean); the pair's term
+ * for that frame is sqrt(var / (f + 1)) / mean where i != j and var > 0.  lindemann_atom (F, N) f64: [f, i] = the sum of atom i's
+ * terms / (N - 1); lindemann_frame (F) f64: [f] = the sum of all terms i != j / (N (N - 1)).  pair_mean / pair_var (N x N f64,
+ * both NULL or both given) receive the full symmetric state after the last frame (zeros on the diagonal).
+ * segments: the j blocks (64 atoms each) of one block of 64 i atoms are shared among this many workgroups, whose row sums are
+ * added in index order afterwards; 0 = the library chooses (enough workgroups to fill the device when N is a few thousand);
+ * always clamped to the number of j blocks, and lowered until the row sums — segments x F x N x 8 bytes of scratch — fit
+ * 256 MiB.  Results of different segment counts differ in the last bits; those of one count do not. */
+int mdh_lindemann_all(const double *pos, int64_t F, int64_t N, double *pair_mean, double *pair_var, double *lindemann_frame,
+                      double *lindemann_atom, int segments, int space, void *stream);
+
 /* ---- _repeat_cell ----------------------------------------------------- */
 /* replaces _repeat_cell.repeat_cell                        src/repeat_cell.cpp:19-61; new_pos flat (n_old*nx*ny*nz*3) */
 int mdh_repeat_cell(double *new_pos, const double *old_box9_host, const double *old_pos, int64_t n_old, int nx,

@@ -18,6 +18,7 @@ from .warren_cowley_parameter import WarrenCowleyParameter
 from .atomic_strain import AtomicStrain
 from .chill_plus import ChillPlus
 from .wigner_seitz_defect import WignerSeitzAnalysis
+from .lindemann_parameter import LindemannParameter
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -25,6 +26,6 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis",
+    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]
