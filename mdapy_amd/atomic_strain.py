@@ -15,7 +15,7 @@ Two things the reference leaves open:
   (``self.repeat``); the first ``N`` rows are stored.
 * **an atom without neighbours** gets what the formulas give: shear 0, volumetric -0.5.
 
-When ``ref`` is large and was handed in in no spatial order its list was built on the cell-sorted twin (system.py).  The
+When ``ref`` is large and was handed in in no spatial order its list was built on the cell-sorted twin (_twin.py).  The
 kernel then runs on the twin's rows and positions, ``current`` is read through the twin's permutation, and the two result
 columns are scattered back: the N x M rows are never translated, and no gather goes through a shuffled numbering.  A row lists
 the same atoms in the same order either way, so the sums are the same bit for bit."""
@@ -49,9 +49,8 @@ class AtomicStrain:
     def _reference(self):
         """(rows, counts, box, position columns, permutation or None) the strain is computed over"""
         ref = self.ref
-        state = ref.__dict__.get("_twin_state")
-        if state is not None and state[1] is not None and ref._mirrors_twin() and "verlet_list" in state[1].__dict__:
-            twin = state[1]  # the list lives on the cell-sorted twin; ref.verlet_list is its untranslated mirror
+        twin = ref._listed_on_twin()
+        if twin is not None:  # the list lives on the cell-sorted twin; ref.verlet_list is its untranslated mirror
             return twin.verlet_list, twin.neighbor_number, ref.box, policy.positions(twin.data), twin._perm
         cell, frame = ref._get_compute_view()
         return ref.verlet_list, ref.neighbor_number, cell, policy.positions(frame), None
@@ -68,7 +67,7 @@ class AtomicStrain:
         assert current.N == self.ref.N
         rows, counts, ref_box, ref_cols, perm = self._reference()
         cur_data, cur_box = current.data, current.box
-        if "_enlarge_data" in self.ref.__dict__ and perm is None and not policy.is_single(self.repeat):
+        if hasattr(self.ref, "_enlarge_data") and perm is None and not policy.is_single(self.repeat):
             cur_data, cur_box = tool._replicate_pos(current.data, current.box, *self.repeat)
         cur_cols = policy.positions(cur_data)
         atoms = int(rows.shape[0])

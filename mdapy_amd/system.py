@@ -13,6 +13,11 @@ the result object.  The reuse rules are three helpers here — ``_require_cutoff
 
 The lists stay in HBM between calls (:class:`mdapy_amd.devarray.HArray`) and turn into numpy on first host access.
 """
+import functools
+import os
+import warnings
+import weakref
+
 import numpy as np
 
 from . import policy
@@ -27,7 +32,7 @@ from .chill_plus import ChillPlus
 from .cluster_analysis import ClusterAnalysis
 from .common_neighbor_analysis import CommonNeighborAnalysis
 from .common_neighbor_parameter import CommonNeighborParameter
-from .devarray import HArray, as_numpy, full
+from .devarray import HArray, as_numpy, full, have_gpu, torch
 from .frame import Frame
 from .identify_diamond_structure import IdentifyDiamondStructure
 from .identify_fcc_planar_faults import IdentifyFccPlanarFaults
@@ -38,91 +43,34 @@ from .radial_distribution_function import RadialDistributionFunction
 from .steinhardt_bond_orientation import SteinhardtBondOrientation
 from .structure_entropy import StructureEntropy
 from .structure_factor import StructureFactor
+from ._twin import SORT_FAR_FRACTION, Twin, adf_reach  # noqa: F401 (the threshold stays importable from here)
 from .voronoi import Voronoi
 from .warren_cowley_parameter import WarrenCowleyParameter
 
 _REPLICA = ("_enlarge_box", "_enlarge_data")
 _LIST = ("verlet_list", "neighbor_number", "distance_list", "rc", "_sorted_columns", "_list_cutoff") + _REPLICA
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# The cell-sorted twin.  The reference's kernels do not care in which order atoms arrive (a linked list per cell,
-# src/neighbor.cpp:64-100); a GPU's gathers do: on an id-sorted dump of a diffused system, or a shuffled one, a neighbour's
-# position is an HBM access instead of an L2 hit, and the fixed-cutoff CNA of 10 M such atoms took 6.7 ms instead of 0.54
-# (profiles/r05_order_sweep.txt).  A large system that was handed in in no spatial order therefore gets a TWIN: the same atoms
-# in cell order (csrc/order.hip), with every other column read through the permutation.  List builds and the analyses that do
-# not depend on atom numbering run on the twin — lists keyed by the original index, so rows come out in the reference's order
-# and every sum runs over the same numbers in the same order — and what the user reads is translated back: per-atom columns
-# by one scatter, the rows of a list only if somebody asks for them (devarray.LazyHArray).  MDAPY_SPATIAL_SORT = 0 (never),
-# 1 (always, whatever the order looks like; any size — tests), unset (systems of MDAPY_SORT_MIN_ATOMS atoms and more whose
-# order statistic says so).
-# ----------------------------------------------------------------------------------------------------------------------
-import functools
-import os
-
-SORT_MIN_ATOMS = int(os.environ.get("MDAPY_SORT_MIN_ATOMS", "200000"))
-SORT_FAR_FRACTION = 0.25  # of consecutive atoms in bins that do not touch (mdh_order_statistic): a lattice builder's order has < 0.01
+_NAMES = {}  # method -> its positional parameter names (filled by _on_twin; what System._twin_for reads a call's arguments by)
 
 
 def _on_twin(method):
-    """run a System method on the cell-sorted twin when there is one (and the call's arguments allow it); copy back what it left"""
-    name = method.__name__
+    """run a System method on the cell-sorted twin (_twin.py) when there is one and the call's arguments allow it"""
+    name, code = method.__name__, method.__code__
+    _NAMES[name] = code.co_varnames[1:code.co_argcount]  # (taken from the function, once)
 
     @functools.wraps(method)
     def call(self, *args, **kwargs):
         twin = self._twin_for(name, args, kwargs)
-        if twin is None:
-            return method(self, *args, **kwargs)
-        return self._run_on_twin(twin, name, args, kwargs)
+        return method(self, *args, **kwargs) if twin is None else self._run_on_twin(twin, name, args, kwargs)
 
     return call
-
-
-def _dev_of(harray):
-    return harray.dev()
-
-
-# positional parameter names of the methods that may run on the twin (what _twin_for looks at)
-_ARGS = {
-    "build_neighbor": ("rc", "max_neigh"),
-    "build_nearest_neighbor": ("k",),
-    "cal_common_neighbor_analysis": ("rc", "max_neigh"),
-    "cal_common_neighbor_parameter": ("rc", "max_neigh"),
-    "cal_structure_entropy": ("rc", "sigma", "use_local_density", "average_rc", "max_neigh"),
-    "cal_atomic_temperature": ("rc", "factor", "max_neigh"),
-    "cal_chill_plus": ("cutoff",),
-    "cal_steinhardt_bond_orientation": ("llist", "use_voronoi", "nnn", "rc", "average", "use_weight", "weight", "wl", "wlhat",
-                                        "a_face_area_threshold", "r_face_area_threshold", "identify_liquid"),
-    "cal_radial_distribution_function": ("rc", "nbin", "max_neigh", "streaming"),
-    "cal_warren_cowley_parameter": ("rc", "max_neigh"),
-    "cal_bond_analysis": ("rc", "nbin", "max_neigh"),
-    "cal_angular_distribution_function": ("rc_dict", "nbin", "max_neigh"),
-    "average_by_neighbor": ("average_rc", "property_name"),
-}
-
-
-def _adf_reach(rc_dict):
-    """the list cutoff of an angular distribution function: the largest number of all its ranges (system.py:2214); None if
-    there is none to read"""
-    try:
-        values = np.asarray(list(rc_dict.values()), dtype=float)
-        return float(values.max()) if values.size else None
-    except (AttributeError, TypeError, ValueError):
-        return None
 
 
 def _position_columns(xyz):
     """x, y, z columns of an (N, 3) array.  With a GPU the array crosses PCIe once, as it is, and is split into columns in HBM
     (the columns' host copies are made if somebody asks for them): the three strided host copies of the reference's
     pos[:, k] pattern were 70 of the 90 ms a 10 M-atom numpy-in / labels-out call took."""
-    from .devarray import have_gpu
-
     if have_gpu() and xyz.shape[0] >= (1 << 16):
-        from .devarray import HArray, torch
-
         t = torch()
-        import warnings
-
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")  # (a read-only source array: the tensor is only read)
             dev = t.from_numpy(np.ascontiguousarray(xyz)).to("cuda")
@@ -183,47 +131,6 @@ def _from_ovito(collection):
     return Frame(cols), cell, info
 
 
-# The frames of a trajectory share their atom numbering: when a System has just been sorted and the next one brings as many atoms in
-# the same box shape, its positions are first read through the LAST permutation — atoms move a fraction of a cell between frames, the
-# old cell order is still a spatial order — and the order statistic of the result decides whether that will do (three gathers and a
-# sampling pass instead of a sort: the sort is as long as the whole neighbor + CNA step of an ordered frame).
-_last_order = {}  # "perm": HArray / ndarray, "n": atoms, "pbc": tuple
-
-
-def _remember_order(perm, n, where):
-    _last_order.update(perm=perm, n=int(n), pbc=tuple(int(v) for v in np.asarray(where[5]).ravel()), host=isinstance(perm, np.ndarray))
-
-
-def _sorted_as_last_time(cols, where, n):
-    from . import kernels
-
-    perm = _last_order.get("perm")
-    if perm is None or _last_order.get("n") != int(n) or os.environ.get("MDAPY_REUSE_ORDER", "1") == "0":
-        return None
-    if _last_order.get("pbc") != tuple(int(v) for v in np.asarray(where[5]).ravel()):
-        return None
-    on_dev = any(c._host_arr is None or c._dev is not None for c in cols)
-    if on_dev == bool(_last_order.get("host")):
-        return None  # (the permutation lives in the other memory space)
-    arrs = [c.device_array() if on_dev else c.to_numpy() for c in cols]
-    if hasattr(kernels.order, "gather_positions"):
-        moved = list(kernels.order.gather_positions(*arrs, perm))
-    else:
-        moved = [kernels.order.permute(a, perm) for a in arrs]
-    # an absent atom (a coordinate that is NaN; infinite ones with it) is binned by neither the statistic nor a sort: the sort reports
-    # fewer atoms than N and the caller makes no twin — so must this path, which never counts (a sum of finite numbers that overflows
-    # only sends the frame to the sort)
-    if on_dev:
-        total = sum(m.dev().sum() for m in moved)
-        if not bool(total.isfinite()):
-            return None
-    elif not np.isfinite(sum(float(np.sum(m)) for m in moved)):
-        return None
-    if kernels.order.order_statistic(*moved, *where[3:]) > SORT_FAR_FRACTION:
-        return None  # another numbering after all: sort
-    return moved[0], moved[1], moved[2], perm, int(n)
-
-
 class System:
     def __init__(self, filename=None, data=None, pos=None, box=None, ase_atom=None, ovito_atom=None, format=None,
                  global_info=None):
@@ -258,175 +165,42 @@ class System:
     def _forget(self, names):
         for name in names:
             self.__dict__.pop(name, None)
-        if "verlet_list" in names:  # the list is gone: the twin's too, and what mirrored it
-            state = self.__dict__.get("_twin_state")
-            if state is not None and state[1] is not None:
-                state[1]._forget(_LIST)
-            self.__dict__.pop("_mirror", None)
+        if "verlet_list" in names and self._twin is not None:  # the list is gone: the twin's too, and what mirrored it
+            self._twin.forget_lists()
 
-    # ------------------------------------------------------- the cell-sorted twin (see the top of the module)
+    def _forget_list(self):
+        self._forget(_LIST)
+
+    # ------------------------------------------------------- the cell-sorted twin: all but these doors is in _twin.py
+    _twin = None     # not decided yet; then a Twin — whose `system` is None where these columns and this box get none
+    _twin_of = None  # on the sorted System of a Twin (which gets no twin of its own): a weak reference back to it
+    _perm = property(lambda self: self._twin_of and self._twin_of().perm)  # (of a sorted System: its row p is atom perm[p] of the owner)
+
     def _spatial(self):
-        """the twin, made on first use; None: this system is analysed in the order it has"""
-        if self.__dict__.get("_is_twin"):
+        """the twin — the sorted System of `_twin` — made on first use; None: this system is analysed in the order it has"""
+        if self._twin_of is not None or self._sort_mode == "0":
             return None
-        mode = self.__dict__.get("_sort_mode", "")
-        if mode == "0":
-            return None
-        cols = tuple(self._frame[c] for c in ("x", "y", "z"))
-        # (the twin belongs to THESE column objects and THIS box: the state keeps them alive, so that "the same object" cannot be a
-        # new one at a recycled address)
-        key = (*cols, self._cell)
-        state = self.__dict__.get("_twin_state")
-        if state is not None and len(state[0]) == len(key) and all(a is b for a, b in zip(state[0], key)):
-            return state[1]
-        twin = None
-        from .devarray import have_gpu
-        from . import kernels
-
-        big = self.N >= SORT_MIN_ATOMS or (mode == "1" and self.N >= 2)
-        if big and hasattr(kernels, "order") and (have_gpu() or mode == "1") and all(np.dtype(c.dtype) == np.float64 for c in cols) \
-                and policy.is_single(self._safe_repeat()):
-            where = (*cols, *policy.box_args(self.box))
-            if mode == "1" or kernels.order.order_statistic(*where) > SORT_FAR_FRACTION:
-                xs, ys, zs, perm, n = _sorted_as_last_time(cols, where, self.N) or kernels.order.spatial_sort(*where)
-                if n == self.N:
-                    _remember_order(perm, self.N, where)
-                    twin = System(data=Frame({"x": xs, "y": ys, "z": zs}), box=self.box)
-                    twin._is_twin = True
-                    twin._perm = perm
-                    # the in-cell ordering key of the twin's list builds: the ORIGINAL index, so that a row lists its atoms in the
-                    # order the reference would (descending index inside a cell, neighbor.cpp:97-98)
-                    twin._order_key = (HArray(perm.dev().long()) if isinstance(perm, HArray) else np.asarray(perm, np.int64))
-        self._twin_state = (key, twin)
-        self.__dict__.pop("_mirror", None)
-        self.__dict__.pop("_twin_cols", None)
-        return twin
+        twin, mine = self._twin, (self._frame["x"], self._frame["y"], self._frame["z"], self._cell)
+        if twin is None or any(a is not b for a, b in zip(twin.made_from, mine)):
+            twin = self._twin = Twin(self)
+        return twin.system
 
     def _mirrors_twin(self):
-        """whether the list this system remembers is the twin's list, translated, rows in the twin's order.  Sorting the front
-        columns of the mirror in place would leave the same object with other rows than the twin's — and sums, and an ADF whose
-        two ranges differ, depend on the order of a row.  ``_sort_front`` therefore sorts the twin's rows and mirrors them again;
-        were the two ever out of step all the same, the analyses run on this system itself (its list is complete)"""
-        mirror, mine = self.__dict__.get("_mirror"), self.__dict__.get("verlet_list")
-        return mirror is not None and mine is mirror["rows"] \
-            and self.__dict__.get("_sorted_columns", (None, 0)) == (id(mine), mirror["state"][3])
+        """whether the list this system remembers is the twin's list, translated, rows in the twin's order (Twin.mirrors)"""
+        return self._twin is not None and self._twin.mirrors(self)
+
+    def _listed_on_twin(self):
+        """the twin, when the list this system remembers is the twin's list, translated and in step, and the twin still has it"""
+        return self._twin.system if self._twin is not None and self._twin.listed(self) else None
 
     def _twin_for(self, name, args, kwargs):
-        """the twin if method ``name`` may run on it with these arguments"""
+        """the twin if method ``name`` may run on it with these arguments (only what the caller passed is bound: no defaults)"""
         twin = self._spatial()
-        if twin is None:
-            return None
-        # the list this system remembers must be the twin's (translated), or neither has one
-        mine = self.__dict__.get("verlet_list")
-        if mine is not None and not self._mirrors_twin():
-            return None
-        if mine is None and "verlet_list" in twin.__dict__:
-            twin._forget(_LIST)
-        bound = dict(zip(_ARGS.get(name, ()), args), **kwargs)
-        reach = bound.get("rc", bound.get("cutoff", bound.get("average_rc")))
-        if name == "cal_angular_distribution_function":
-            reach = _adf_reach(bound.get("rc_dict"))
-        if name in ("cal_bond_analysis", "cal_angular_distribution_function") and isinstance(reach, (int, float, np.integer, np.floating)) \
-                and "rc" in self.__dict__ and self.rc >= reach and "_list_cutoff" not in self.__dict__:
-            return None  # (a k-nearest list beside a stale rc is reused as it is: its rows are not symmetric, so j > i depends on numbering)
-        if isinstance(reach, (int, float, np.integer, np.floating)) and reach > 0 and \
-                not policy.is_single(policy.axis_copies(self.box, 2.0 * float(reach))):
-            return None  # the build would search a replica: the ordering key cannot follow
-        if name == "cal_steinhardt_bond_orientation" and (bound.get("use_voronoi") or bound.get("identify_liquid")
-                                                         or bound.get("weight") is not None):
-            return None  # (a caller's weight array lines up with THIS system's rows, not with the twin's permuted ones)
-        return twin
+        return twin if twin is not None and self._twin.may_run(self, name, dict(zip(_NAMES.get(name, ()), args), **kwargs)) else None
 
     def _run_on_twin(self, twin, name, args, kwargs):
-        from . import kernels
-        from .devarray import LazyHArray
-        from .frame import PermutedColumn
-
-        perm = twin._perm
-        # every column the twin does not have yet, read through the permutation (nothing moves before a kernel asks)
-        cache = self.__dict__.setdefault("_twin_cols", {})
-        cols = {}
-        for cname in twin._frame.columns[:3]:
-            cols[cname] = twin._frame[cname]
-        for cname in self._frame.columns:
-            if cname in ("x", "y", "z"):
-                continue
-            src = self._frame[cname]
-            hit = cache.get(cname)
-            if hit is None or hit[0] is not src:
-                hit = cache[cname] = (src, PermutedColumn(src, perm))
-            cols[cname] = hit[1]
-        twin._frame = Frame(cols)
-        twin._frame.order_key = twin._order_key  # (what a k-nearest search on this frame breaks exact ties by: knn.py)
-        before = {cname: twin._frame[cname] for cname in twin._frame.columns}
-        result = getattr(twin, name)(*args, **kwargs)
-        # per-atom results: columns the call added or replaced, back in this system's order
-        restored = {}
-        for cname in twin._frame.columns:
-            col = twin._frame[cname]
-            if before.get(cname) is col:
-                continue
-            kind = np.dtype(col.dtype)
-            if col._host_arr is None and kind.kind in "iuf" and kind.itemsize in (4, 8):
-                restored[cname] = kernels.order.permute(col.device_array(), perm, scatter=True)
-            else:
-                out = np.empty_like(col.to_numpy())
-                out[np.asarray(perm)] = col.to_numpy()
-                restored[cname] = out
-        if restored:
-            self.update_data(self._frame.with_columns(**restored))
-        for attr in ("cluster_number",):
-            if attr in twin.__dict__:
-                setattr(self, attr, twin.__dict__[attr])
-        # the list the twin remembers now, as this system's: translated when somebody reads it
-        self._mirror_lists(twin)
-        if "ptm_indices" in twin.__dict__ and name == "cal_polyhedral_template_matching":
-            src = twin.ptm_indices
-            self.ptm_indices = LazyHArray(lambda: _dev_of(kernels.order.translate_rows(src, None, None, perm)[0]), src.shape, np.int32) \
-                if isinstance(src, HArray) else kernels.order.translate_rows(np.asarray(src), None, None, np.asarray(perm))[0]
-        if name == "build_neighbor" and result is not None:  # the labels of build_neighbor(..., _label=True): per atom, the twin's order
-            result = kernels.order.permute(result, perm, scatter=True)
-        return result
-
-    def _mirror_lists(self, twin):
-        from . import kernels
-        from .devarray import LazyHArray
-
-        if "verlet_list" not in twin.__dict__:
-            for attr in _LIST:
-                self.__dict__.pop(attr, None)
-            self.__dict__.pop("_mirror", None)
-            return
-        rows, dist, counts = twin.verlet_list, twin.distance_list, twin.neighbor_number
-        state = (rows, dist, counts, twin.__dict__.get("_sorted_columns", (None, 0))[1])  # (the objects themselves: see _spatial)
-        mirror = self.__dict__.get("_mirror")
-        same = mirror is not None and all(a is b for a, b in zip(mirror["state"][:3], state[:3])) and mirror["state"][3] == state[3]
-        if not same or self.__dict__.get("verlet_list") is not mirror["rows"]:
-            perm = twin._perm
-            done = {}
-
-            def translated(k):
-                if not done:
-                    done["v"], done["d"], done["n"] = kernels.order.translate_rows(rows, dist, counts, perm)
-                return done[k]
-
-            if isinstance(rows, HArray):
-                out = (LazyHArray(lambda: _dev_of(translated("v")), rows.shape, np.int32),
-                       LazyHArray(lambda: _dev_of(translated("d")), dist.shape, np.float64),
-                       # (the counts alone: `_deep_enough` and the overflow check read them; the N x M rows need not move for that)
-                       LazyHArray(lambda: _dev_of(done["n"] if done else kernels.order.permute(counts, perm, scatter=True)), counts.shape, np.int32))
-            else:
-                out = (translated("v"), translated("d"), translated("n"))
-            mirror = self._mirror = {"state": state, "rows": out[0]}
-            self.verlet_list, self.distance_list, self.neighbor_number = out
-        for attr in ("rc", "_list_cutoff"):
-            if attr in twin.__dict__:
-                setattr(self, attr, twin.__dict__[attr])
-            else:
-                self.__dict__.pop(attr, None)
-        self._sorted_columns = (id(self.verlet_list), twin.__dict__.get("_sorted_columns", (None, 0))[1])
-        for attr in _REPLICA:
-            self.__dict__.pop(attr, None)
+        """the one path every call on the twin takes"""
+        return self._twin.run(self, name, args, kwargs)
 
     @property
     def box(self):
@@ -436,7 +210,7 @@ class System:
     def box(self, value):
         # Cartesian coordinates stay as they are; everything computed with the old box is gone
         self._cell = value if isinstance(value, Box) else Box(value)
-        self._forget(_LIST)
+        self._forget_list()
 
     data = property(lambda self: self._frame)
     global_info = property(lambda self: self._info)
@@ -450,13 +224,11 @@ class System:
         reference's deprecated misspelling of ``reset_calculator`` (system.py:686-744), accepted with the same warning; there
         is no calculator on this path, so neither flag has anything to clear."""
         if reset_calcolator is not None:
-            import warnings
-
             warnings.warn("`reset_calcolator` is a misspelling and is deprecated; use `reset_calculator` instead.",
                           DeprecationWarning, stacklevel=2)
         self._frame = Frame.from_any(data)
         if reset_neighbor:
-            self._forget(_LIST)
+            self._forget_list()
 
     def _get_compute_view(self):
         """(box, frame) the remembered list's indices refer to: the replica if there is one"""
@@ -554,7 +326,7 @@ class System:
         self._frame, self.box = tool.replicate(self._frame, self.box, nx, ny, nz)
 
     # ------------------------------------------------------- neighbor lists
-    def _remember(self, search, rows, distances, counts):
+    def _remember(self, search, rows, distances, counts, front=0):
         """take over the list a search object built, and its replica if it made one (the replica always belongs to the
         list that is current: one left behind by an earlier search would be paired with rows it does not describe)"""
         self._forget(_REPLICA)
@@ -562,28 +334,33 @@ class System:
             if name in search.__dict__:
                 setattr(self, name, getattr(search, name))
         self.verlet_list, self.distance_list, self.neighbor_number = rows, distances, counts
-        self._sorted_columns = (id(rows), 0)  # (the list it speaks of, leading columns known to hold the nearest neighbours in order)
+        self._sorted_columns = (weakref.ref(rows), front)  # (THIS list object, weakly; its leading columns known to hold the nearest in order)
+
+    def _front(self):
+        """how many leading columns of the CURRENT list are known to hold the nearest neighbours, in order; -1: nothing known"""
+        which, done = self.__dict__.get("_sorted_columns", (None, -1))
+        rows = which() if which is not None else None
+        return done if rows is not None and rows is self.__dict__.get("verlet_list") else -1
 
     def _sort_front(self, k):
         """the k nearest of every row to the front, nearest first — once: a row prefix that is already in order (the rows of a
         k-nearest search, or an earlier call) is not touched again"""
-        which, done = self.__dict__.get("_sorted_columns", (None, 0))
-        if which != id(self.verlet_list) or done < k:
-            state = self.__dict__.get("_twin_state")
-            if state is not None and state[1] is not None and self._mirrors_twin() and "verlet_list" in state[1].__dict__:
+        if self._front() < k:
+            twin = self._listed_on_twin()
+            if twin is not None:
                 # the list is the twin's, translated: sort the twin's rows and mirror them again, so that the two stay in step and
                 # later analyses keep running on the twin (the selection looks at distances and slots, not at what the entries
                 # are called: the twin's sorted rows, translated, are this system's rows, sorted)
-                state[1]._sort_front(k)
-                self._mirror_lists(state[1])
+                twin._sort_front(k)
+                self._twin.mirror_lists(self)
                 return
             tool.sort_neighbor(self.verlet_list, self.distance_list, self.neighbor_number, k)
-            self._sorted_columns = (id(self.verlet_list), k)
+            self._sorted_columns = (weakref.ref(self.verlet_list), k)
 
     @_on_twin
     def build_neighbor(self, rc, max_neigh=None, _label=False):
         # _label (internal): the fixed-cutoff common-neighbour labels of this cutoff in the same pass; returned, not stored
-        search = Neighbor(rc, self.box, self.data, max_neigh, key=self.__dict__.get("_order_key"))
+        search = Neighbor(rc, self.box, self.data, max_neigh, key=self._twin_of().order_key if self._twin_of is not None else None)
         search.compute(label=_label)
         self.rc = rc
         self._remember(search, search.verlet_list, search.distance_list, search.neighbor_number)
@@ -598,9 +375,8 @@ class System:
         search = NearestNeighbor(self.data, self.box, k)
         search.compute()
         # (the counts live where the rows live: a host array here was 40 MB over PCIe in front of every analysis that takes the list)
-        self._remember(search, search.indices_py, search.distances_py, full((search.indices_py.shape[0],), k, np.int32))
+        self._remember(search, search.indices_py, search.distances_py, full((search.indices_py.shape[0],), k, np.int32), front=k)
         self._forget(("_list_cutoff",))  # the current list is no cutoff list any more (`rc` stays, as in the reference)
-        self._sorted_columns = (id(self.verlet_list), k)
 
     def _require_cutoff_list(self, rc, max_neigh):
         """a cutoff list reaching at least rc: the remembered one if it does, a new one otherwise"""
@@ -660,12 +436,12 @@ class System:
                                          return_rmsd=False, return_atomic_distance=False, return_orientation=False,
                                          identify_fcc_planar_faults=False, identify_esf=True):
         """column ``ptm`` and, on request, ``ordering``, ``rmsd``, ``interatomic_distance``, ``qx qy qz qw``, ``pft``"""
-        twin = self._twin_for("cal_polyhedral_template_matching", (), {})
+        # the two calls of `_on_twin`, the twin's without the planar-fault sweep (its answer depends on the atom numbering: an index-
+        # ordered sweep, identify_fcc_planar_faults.cpp:139-180): that runs here, on the translated labels and template-ordered neighbours
+        matching = (structure, rmsd_threshold, return_ordering, return_rmsd, return_atomic_distance, return_orientation, False, identify_esf)
+        twin = self._twin_for("cal_polyhedral_template_matching", matching, {})
         if twin is not None:
-            # the matching on the twin; the planar-fault sweep (its answer depends on the atom numbering: an index-ordered sweep,
-            # identify_fcc_planar_faults.cpp:139-180) here, on the translated labels and template-ordered neighbours
-            self._run_on_twin(twin, "cal_polyhedral_template_matching", (structure, rmsd_threshold, return_ordering, return_rmsd,
-                                                                        return_atomic_distance, return_orientation, False, identify_esf), {})
+            self._run_on_twin(twin, "cal_polyhedral_template_matching", matching, {})
             if identify_fcc_planar_faults:
                 shell = np.ascontiguousarray(as_numpy(self.ptm_indices)[:, 1:13])
                 faults = IdentifyFccPlanarFaults(np.array(self.data["ptm"].to_numpy(), np.int32), shell, identify_esf)
@@ -897,7 +673,7 @@ class System:
         """-> AngularDistributionFunction (``bond_angle_distribution`` npattern x nbin, int64, ``r_angle``).  ``rc_dict`` maps
         ``"A-B-C"`` (A the centre) to ``[rij_min, rij_max, rik_min, rik_max]``"""
         assert "element" in self.data.columns, "Data must contain element column."
-        rc = _adf_reach(rc_dict)
+        rc = adf_reach(rc_dict)
         if rc is None:
             raise ValueError("rc_dict must map 'A-B-C' patterns to [rij_min, rij_max, rik_min, rik_max].")
         if not rc > 0:

@@ -116,7 +116,7 @@ def test_shuffled_atoms_run_on_the_twin(restated, monkeypatch):
     monkeypatch.setenv("MDAPY_SPATIAL_SORT", "1")
     s = mp.System(pos=pos[order], box=box)
     s.cal_chill_plus()
-    assert s._spatial() is not None and s.__dict__["_mirror"]["rows"] is s.verlet_list and s.rc == 3.5
+    assert s._spatial() is not None and s._twin.shown.mirror is s.verlet_list and s.rc == 3.5
     assert np.array_equal(_labels(s), _labels(plain)[order])
     # a box thinner than two cutoffs stays off the twin (the reach is read from ``cutoff``): its list is the replica's
     cell, cell_box = lattice_positions("diamond", 6.37, 3, 3, 3)  # 19.11 A
@@ -124,7 +124,7 @@ def test_shuffled_atoms_run_on_the_twin(restated, monkeypatch):
     assert small._spatial() is not None and small._twin_for("cal_chill_plus", (), {}) is small._spatial()
     assert small._twin_for("cal_chill_plus", (10.0,), {}) is None and small._twin_for("cal_chill_plus", (), {"cutoff": 10.0}) is None
     small.cal_chill_plus(10.0)
-    assert "_enlarge_data" in small.__dict__ and "_mirror" not in small.__dict__ and _labels(small).shape == (216,)
+    assert "_enlarge_data" in small.__dict__ and small._twin.shown is None and _labels(small).shape == (216,)
 
 
 def test_lonsdaleite_cell():

@@ -254,7 +254,7 @@ def test_shuffled_atoms_on_the_twin_and_off_it():
         s.cal_chill_plus()
         got[mode] = _labels(s)
         if mode == "1":
-            assert s.__dict__["_mirror"]["rows"] is s.verlet_list
+            assert s._twin.shown.mirror is s.verlet_list
         _chill_ref.check(got[mode], *_chill_ref.on_system_list(s, 3.5)[::2], f"shuffled, sort={mode}")
     # the twin's rows are keyed by the original index: the same sums in the same order, the same labels bit for bit
     assert np.array_equal(got["1"], got["0"])

@@ -210,3 +210,11 @@ def test_next_frame_of_a_trajectory_is_read_through_the_last_permutation():
     s.cal_common_neighbor_analysis(rc=rc)
     assert s._spatial() is not None and not np.array_equal(np.asarray(as_numpy(s._spatial()._perm)), perms[0])
     assert int((s.data["cna"].to_numpy() == 1).sum()) > 0.9 * len(pos)
+
+
+def test_edges_between_a_system_and_its_twin_in_one_sequence():
+    """tests/_twin_walk.py on the kernels: 1 008 shuffled atoms on the twin (MDAPY_SPATIAL_SORT=1) against the same system as it is
+    (=0) — lists and columns bit for bit after every step, with which side ran and ``_listed_on_twin`` asserted"""
+    import _twin_walk
+
+    _twin_walk.walk()

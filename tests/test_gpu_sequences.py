@@ -5,7 +5,7 @@ analysis is used on a sequence of different frames.  The frames come from tests/
 the oracle's on that frame alone, and every comparison is bitwise (rattled crystals and gases: no exact ties in distance).
 
   B1  neighbor_cna_step(..., reuse_buffers=True): the four result arrays kept on the decomposition
-  B2  System after System: the permutation of the last sorted System (system.py _last_order)
+  B2  System after System: the permutation of the last sorted System (_twin.py _last)
   B3  the k-nearest searches of one System that share candidate rows (knn.py), and the signature table of knn.hip
   B4  atoms the rows build does not bin (counts of the rows build)"""
 import ctypes
@@ -210,10 +210,10 @@ def _system(frame, space):
 
 
 def _analyse(frames, spaces, rc, k):
-    from mdapy_amd import system as system_mod
+    from mdapy_amd import _twin as twin_mod
     from mdapy_amd.devarray import as_numpy
 
-    system_mod._last_order.clear()
+    twin_mod.forget_order()
     out, last = [], None
     for f, space in zip(frames, spaces):
         s = _system(f, space)
@@ -245,10 +245,10 @@ def test_system_after_system_equals_the_oracle_frame_by_frame(monkeypatch, name)
     absent atom (x = NaN) gets no twin whether a permutation is remembered or not (tests/test_gpu_order.py
     test_absent_atoms_make_the_sort_stand_down is the first frame's contract); its finite atoms' results equal the oracle's over the
     finite atoms, its own k-nearest row is not compared here (B4 pins it)."""
-    from mdapy_amd import system as system_mod
+    from mdapy_amd import _twin as twin_mod
 
     monkeypatch.delenv("MDAPY_SPATIAL_SORT", raising=False)
-    monkeypatch.setattr(system_mod, "SORT_MIN_ATOMS", 10000)
+    monkeypatch.setattr(twin_mod, "SORT_MIN_ATOMS", 10000)
     first, steps, want, spaces = TRAJECTORIES[name]
     f0 = first()
     rc = RC_CNA if f0.n != 16000 else 1.2 * 2.87  # (bcc: first and second shell)

@@ -253,25 +253,25 @@ def test_current_columns_in_hbm_equal_host_columns():
 
 @pytest.mark.parametrize("affine", [False, True])
 def test_shuffled_frames_run_on_the_twin_without_translating_its_rows(affine):
-    from mdapy_amd import system as system_mod
+    from mdapy_amd import _twin as twin_mod
     from mdapy_amd.devarray import LazyHArray
 
     cells = 37
     pos, cell = _fcc(cells, 15)
-    assert len(pos) >= system_mod.SORT_MIN_ATOMS
+    assert len(pos) >= twin_mod.SORT_MIN_ATOMS
     moved, moved_cell = _deformed(pos, cell, 16)
     order = np.random.default_rng(17).permutation(len(pos))
     ref = mp.System(pos=pos[order], box=cell)
     strain = mp.AtomicStrain(3.1, ref, affine=affine)
     assert ref._spatial() is not None, "the shuffled reference has a cell-sorted twin"
-    mirror = ref.__dict__["_mirror"]
-    assert mirror["rows"] is ref.verlet_list and isinstance(ref.verlet_list, LazyHArray)
+    shown = ref._twin.shown
+    assert shown.mirror is ref.verlet_list and isinstance(ref.verlet_list, LazyHArray)
     cur = mp.System(pos=moved[order], box=mp.Box(moved_cell))
     strain.compute(cur)
     second = mp.System(pos=(moved + 0.01)[order], box=mp.Box(moved_cell))
     strain.compute(second)
     assert not ref.verlet_list.produced and not ref.distance_list.produced, "compute translated the N x M rows of the mirror"
-    assert ref.__dict__["_mirror"] is mirror
+    assert ref._twin.shown is shown
     # now the rows are read (and translated): the restatement in the shuffled numbering
     for frame in (cur, second):
         got, want = _columns(frame), _strain_ref.on_system_list(strain, frame)

@@ -153,7 +153,7 @@ def test_perfect_lattice_ties_fall_as_in_the_original_numbering(oracle_backend, 
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# Trajectories: the permutation of the last sorted System is carried to the next one (system.py _last_order / _sorted_as_last_time).
+# Trajectories: the permutation of the last sorted System is carried to the next one (_twin.py _last / _sorted_as_last_time).
 # The oracle backend's order statistic restates mdh_order_statistic, so the decision "read through the old permutation or sort
 # afresh" is the one the HIP path takes; tests/test_gpu_sequences.py runs the same sequences on the kernels.
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -172,9 +172,9 @@ SEQUENCES = {  # steps, and for every frame: "sort" (a fresh permutation), "reus
 
 def _run_sequence(frames, analyse):
     """one System per frame, as a trajectory loop makes them -> per frame (what happened to the permutation, results or None)"""
-    from mdapy_amd import system as system_mod
+    from mdapy_amd import _twin as twin_mod
 
-    system_mod._last_order.clear()
+    twin_mod.forget_order()
     out, last = [], None
     for f in frames:
         s = mp.System(pos=f.pos, box=mp.Box(f.box, boundary=[int(b) for b in f.boundary], origin=f.origin))
@@ -239,3 +239,87 @@ def test_order_statistic_of_the_oracle_backend_tells_a_spatial_order_from_a_shuf
     h = T.nan_atom(g, np.random.default_rng(7))
     assert K.order.spatial_sort(*h.where())[4] == h.n - 1
     assert 0.7 < K.order.order_statistic(*h.where()) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The state between a System and its twin is one object (mdapy_amd/_twin.py): its edges, the names the decorator binds, and the
+# remembered permutation as one record.
+# ------------------------------------------------------------------------------------------------------------------------------
+def test_edges_between_a_system_and_its_twin_in_one_sequence(oracle_backend, monkeypatch):
+    """tests/_twin_walk.py: build, sort the front, ADF, a k-nearest list beside a stale rc, a user's list, a forgotten list, a new
+    box, removed atoms — twin against plain bit for bit after every step, with which side ran and ``_listed_on_twin`` asserted"""
+    import _twin_walk
+
+    oracle_backend.install_consumers(monkeypatch)
+    _twin_walk.walk()
+
+
+def test_the_decorator_binds_the_functions_own_positional_names(oracle_backend, monkeypatch):
+    """``_on_twin`` reads the positional parameter names off the function it wraps; ``_twin_for`` decides the same for a positional, a
+    keyword and a mixed spelling of a call.  ``cal_chill_plus(3.5)`` and ``cal_structure_entropy(4.0, 0.2, False, 3.2)`` run on the
+    twin in every box that has one (a box thinner than their two cutoffs, 7 and 8 A, is below the 15 A under which there is no twin
+    at all).  The decision "no twin" that hangs on finding the reach under its name is therefore taken with 9.5 A in their place: two
+    cutoffs are more than the 18.08 A of the thin box and less than the 21.69 A of the wide one."""
+    import inspect
+
+    from mdapy_amd.system import _NAMES, System
+
+    wrapped = {name for name, member in vars(System).items() if hasattr(member, "__wrapped__")}
+    assert wrapped == set(_NAMES) and len(wrapped) == 15
+    for name in wrapped:
+        params = list(inspect.signature(getattr(System, name).__wrapped__).parameters.values())[1:]
+        assert all(q.kind is q.POSITIONAL_OR_KEYWORD for q in params), name
+        assert _NAMES[name] == tuple(q.name for q in params), name
+    wide = _system(monkeypatch, "1")                   # 25.31 x 21.69 x 21.69 A
+    thin = _system(monkeypatch, "1", cells=(7, 6, 5))  # 18.08 A across z
+    assert wide._spatial() is not None and thin._spatial() is not None
+
+    def decisions(s, name, args):
+        """positional, keyword, and first-positional-rest-keyword spelling -> whether each may run on the twin"""
+        named = dict(zip(_NAMES[name], args))
+        rest = {k: v for k, v in list(named.items())[1:]}
+        got = [s._twin_for(name, args, {}), s._twin_for(name, (), named), s._twin_for(name, args[:1], rest)]
+        assert all(g is None or g is s._spatial() for g in got)
+        return [g is not None for g in got]
+
+    for reach, on_wide, on_thin in ((None, True, True), (9.5, True, False)):
+        for name, args in (("cal_chill_plus", (3.5,)), ("cal_structure_entropy", (4.0, 0.2, False, 3.2)), ("average_by_neighbor", (3.4, "x"))):
+            if reach is not None:
+                args = (reach,) + args[1:]
+            assert decisions(wide, name, args) == [on_wide] * 3, (name, args)
+            assert decisions(thin, name, args) == [on_thin] * 3, (name, args)
+    # the reach is found behind other arguments too, and an argument that was not passed is not read (no defaults: no reach)
+    assert thin._twin_for("cal_steinhardt_bond_orientation", ([6], False, 0, 9.5), {}) is None
+    assert thin._twin_for("cal_steinhardt_bond_orientation", ([6],), dict(nnn=12, max_neigh=60, threshold=0.6)) is thin._spatial()
+    assert thin._twin_for("cal_chill_plus", (), {}) is thin._spatial() and wide._twin_for("cal_chill_plus", (), {}) is wide._spatial()
+
+
+def test_the_remembered_permutation_is_one_record_replaced_whole(oracle_backend, monkeypatch):
+    """after frame A and frame B (another number of atoms; then another pbc) the snapshot a reader takes is wholly A's or wholly
+    B's: the record held before the second sort still carries A's fields, and a new one stands in its place"""
+    from mdapy_amd import _twin as twin_mod
+
+    twin_mod.forget_order()
+    assert twin_mod._last is None
+    a = _system(monkeypatch, "1")
+    ta = a._spatial()
+    rec_a = twin_mod._last
+    assert isinstance(rec_a, tuple) and rec_a._fields == ("perm", "n", "pbc", "host")
+    assert rec_a.perm is ta._perm and rec_a.n == a.N == 1008 and rec_a.pbc == (1, 1, 1) and rec_a.host is True
+    with pytest.raises(AttributeError):
+        rec_a.n = 5
+    b = _system(monkeypatch, "1", cells=(6, 6, 6))  # another N
+    tb = b._spatial()
+    rec_b = twin_mod._last
+    assert rec_b is not rec_a and (rec_b.perm, rec_b.n, rec_b.pbc) == (tb._perm, 864, (1, 1, 1)) and tb._perm is not ta._perm
+    assert rec_a.perm is ta._perm and rec_a.n == 1008 and rec_a.pbc == (1, 1, 1) and len(np.asarray(rec_a.perm)) == rec_a.n
+    pos = np.column_stack([b.data[c].to_numpy() for c in "xyz"])
+    c = mp.System(pos=pos, box=mp.Box(b.box.box, boundary=[1, 0, 1]))  # the same N, another pbc: sorted afresh
+    tc = c._spatial()
+    rec_c = twin_mod._last
+    assert tc._perm is not tb._perm and rec_c is not rec_b and (rec_c.perm, rec_c.n, rec_c.pbc) == (tc._perm, 864, (1, 0, 1))
+    assert (rec_b.perm, rec_b.n, rec_b.pbc) == (tb._perm, 864, (1, 1, 1))
+    for rec in (rec_a, rec_b, rec_c):
+        assert len(np.asarray(rec.perm)) == rec.n
+    twin_mod.forget_order()
+    assert twin_mod._last is None

@@ -171,7 +171,7 @@ def test_shuffled_reference_runs_on_the_twin(restated, monkeypatch):
     for affine in (False, True):
         ref = mp.System(pos=pos[order], box=box)
         strain = mp.AtomicStrain(3.1, ref, affine=affine)
-        assert ref._spatial() is not None and ref.__dict__["_mirror"]["rows"] is ref.verlet_list
+        assert ref._spatial() is not None and ref._twin.shown.mirror is ref.verlet_list
         cur = mp.System(pos=moved[order], box=mp.Box(cell))
         strain.compute(cur)
         want = _direct(strain, cur)  # on the translated rows, in the shuffled numbering

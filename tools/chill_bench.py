@@ -104,7 +104,7 @@ def main():
         list_rc = args.list_rc or args.rc
         out = {"case": tag, "atoms": n, "rc": args.rc, "list_rc": list_rc, "sigma": args.sigma, "build_ms": timed(lambda: s.build_neighbor(list_rc))}
         out["row_width"] = width = int(s.verlet_list.shape[1])
-        out["on_twin"] = s.__dict__.get("_mirror") is not None
+        out["on_twin"] = s._listed_on_twin() is not None
         out["chill"] = laps(lambda: s.cal_chill_plus(args.rc))
         out["temp"] = laps(lambda: s.cal_atomic_temperature(args.rc))
         out["kernels_ms"] = kernel_ms(lambda: s.cal_chill_plus(args.rc), ("k_chill_q", "k_chill_classify"))

@@ -80,7 +80,7 @@ def main():
         out = {"case": tag, "atoms": n, "rc": args.rc, "first_ms": timed(first)}
         strain = state["strain"]
         out["row_width"] = int(ref.verlet_list.shape[1])
-        out["on_twin"] = ref.__dict__.get("_mirror") is not None
+        out["on_twin"] = ref._listed_on_twin() is not None
         out["steady"] = laps(lambda: strain.compute(mp.System(data=cur_frame, box=mp.Box(moved_cell))))
         mapped = mp.AtomicStrain(args.rc, ref, affine=True)  # (builds the list again: not timed)
         out["steady_affine"] = laps(lambda: mapped.compute(mp.System(data=cur_frame, box=mp.Box(moved_cell))))
