@@ -550,6 +550,23 @@ int mdh_lindemann_global(const double *pos, int64_t F, int64_t N, double *pair_s
 int mdh_lindemann_all(const double *pos, int64_t F, int64_t N, double *pair_mean, double *pair_var, double *lindemann_frame,
                       double *lindemann_atom, int segments, int space, void *stream);
 
+/* ---- _msd -------------------------------------------------------------- */
+/* Mean squared displacement of a trajectory.  pos (F, N, 3) f64, C-contiguous, UNWRAPPED positions of F >= 1 frames of N >= 1
+ * atoms.  term(a, b) = (dx*dx + dy*dy) + dz*dz with dx = a.x - b.x, ..., every operation in IEEE binary64 without contraction.
+ * The reference has no compiled module for this (src/mdapy/mean_squared_displacement.py takes S1 - 2 S2 by FFT, which cancels);
+ * the definition itself is summed here.  particle_msd and msd may each be NULL (not wanted), not both; msd carries the same bits
+ * either way.  Sums are taken in a fixed order (no floating-point atomics): the same input gives the same bits on every run, and a
+ * call with fewer lags gives the first rows of the call with more.  Nothing F x F is stored, and nothing N x F besides
+ * particle_msd; scratch is rows x ceil(N / 64) doubles when msd is wanted.  F < 1, N < 1, L outside 1 .. F, pos == NULL or both
+ * outputs NULL return MDH_ERR_ARG before any device work, as do F > 2^24, N > 2^28 and a product too large for one launch.
+ *
+ * window: particle_msd (L, N) f64: [m, i] = (the sum over t = 0 .. F-m-1, in that order, of term(pos[t+m, i], pos[t, i])) /
+ * (F - m) for the lags m = 0 .. L-1, 1 <= L <= F; msd (L) f64: [m] = (the sum over i of particle_msd[m, i]) / N — over the 64
+ * atoms of a block by a butterfly, then over the blocks: 64 running sums of blocks l, l + 64, ... in index order, then a butterfly. */
+int mdh_msd_window(const double *pos, int64_t F, int64_t N, int64_t L, double *particle_msd, double *msd, int space, void *stream);
+/* direct: particle_msd (F, N) f64: [t, i] = term(pos[t, i], pos[0, i]); msd (F) f64 as above */
+int mdh_msd_direct(const double *pos, int64_t F, int64_t N, double *particle_msd, double *msd, int space, void *stream);
+
 /* ---- _repeat_cell ----------------------------------------------------- */
 /* replaces _repeat_cell.repeat_cell                        src/repeat_cell.cpp:19-61; new_pos flat (n_old*nx*ny*nz*3) */
 int mdh_repeat_cell(double *new_pos, const double *old_box9_host, const double *old_pos, int64_t n_old, int nx,

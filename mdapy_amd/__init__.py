@@ -19,6 +19,7 @@ from .atomic_strain import AtomicStrain
 from .chill_plus import ChillPlus
 from .wigner_seitz_defect import WignerSeitzAnalysis
 from .lindemann_parameter import LindemannParameter
+from .mean_squared_displacement import MeanSquaredDisplacement
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -26,6 +27,6 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter",
+    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

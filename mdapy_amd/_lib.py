@@ -112,6 +112,8 @@ _SIGNATURES = {
     "mdh_ws_occupancy": [vp, i64, i64, vp, vp, vp, vp, vp, cint, vp],
     "mdh_lindemann_global": [vp, i64, i64, vp, vp, vp, cint, vp],
     "mdh_lindemann_all": [vp, i64, i64, vp, vp, vp, vp, cint, cint, vp],
+    "mdh_msd_window": [vp, i64, i64, i64, vp, vp, cint, vp],
+    "mdh_msd_direct": [vp, i64, i64, vp, vp, cint, vp],
     "mdh_repeat_cell": [vp, vp, vp, i64, cint, cint, cint, cint, vp],
     "mdh_ptm": [C.c_char_p, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, dbl, vp, cint, vp, cint, cint, vp],
     "mdh_ptm_flags": [C.c_char_p],

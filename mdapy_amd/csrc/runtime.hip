@@ -398,6 +398,7 @@ void warm_wcp(hipStream_t st);
 void warm_knn(hipStream_t st);
 void warm_wigner_seitz(hipStream_t st);
 void warm_lindemann(hipStream_t st);
+void warm_msd(hipStream_t st);
 void warm_repeat(hipStream_t st);
 void warm_ptm(hipStream_t st);
 void warm_ptm_stages(hipStream_t st);
@@ -523,6 +524,7 @@ int mdh_warm(void)
     mdh::warm_knn(nullptr);
     mdh::warm_wigner_seitz(nullptr);
     mdh::warm_lindemann(nullptr);
+    mdh::warm_msd(nullptr);
     mdh::warm_repeat(nullptr);
     mdh::warm_ptm(nullptr);
     mdh::warm_ptm_stages(nullptr);

@@ -20,6 +20,8 @@ from . import _fast_knn as fast_knn
 from . import _fccpft as fccpft
 # (not in NAMES either: the oracle has no Lindemann index; its tests install a restatement as kernels.lindemann)
 from . import _lindemann as lindemann
+# (not in NAMES either: neither the reference nor the oracle has a compiled MSD; its tests install a restatement as kernels.msd)
+from . import _msd as msd
 from . import _neighbor as neighbor
 from . import _order as order
 from . import _polycrystal as polycrystal
