@@ -567,6 +567,35 @@ int mdh_msd_window(const double *pos, int64_t F, int64_t N, int64_t L, double *p
 /* direct: particle_msd (F, N) f64: [t, i] = term(pos[t, i], pos[0, i]); msd (F) f64 as above */
 int mdh_msd_direct(const double *pos, int64_t F, int64_t N, double *particle_msd, double *msd, int space, void *stream);
 
+/* ---- void analysis ------------------------------------------------------ */
+/* replaces _neighbor._fill_cell_for_void (src/neighbor.cpp:780-839) and keeps the rest of mdapy.VoidAnalysis
+ * (src/mdapy/void_analysis.py) on the device.  The grid is the cutoff neighbour build's: ncell[d] = max(floor(thickness[d] / rc), 3)
+ * cells of width rc anchored at the origin, the last one taking the remainder.  Every result is the same on every run: slots of
+ * the two ordered lists come from prefix sums in index order, never from counters.  rc <= 0 or not finite, a singular box and a
+ * grid of more cells than int32 indexes (2 147 483 000) return MDH_ERR_ARG with a message, before any device work.
+ *
+ * mdh_void_grid_dims: ncell3_host (3) i32, host memory; needs no device. */
+int mdh_void_grid_dims(const double *box9, const double *origin3, const int *boundary3, double rc, int *ncell3_host);
+/* cells (ncell0, ncell1, ncell2) i32, row-major, ncell = their product as mdh_void_grid_dims gives it: 1 where at least one atom
+ * falls, 0 elsewhere — the buffer is cleared here.  A position is wrapped into the box iff any axis is periodic, its cell index
+ * floor((x - o) * (1.0 / rc)) (triclinic: floor(frac * thickness * (1.0 / rc))) clamped to [0, ncell - 1]; a NaN coordinate
+ * lands in plane 0 of its axis.  N may be 0. */
+int mdh_fill_cell_for_void(const double *x, const double *y, const double *z, int64_t N, const double *box9, const double *origin3,
+                           const int *boundary3, double rc, int *cells, int64_t ncell, int space, void *stream);
+/* The empty cells (word == 0) of cells (n0, n1, n2) in row-major order (np.argwhere): *count_host (host memory) = how many; with
+ * cx, cy, cz (cap) f64 given, point k = the centre of the k-th empty cell (i0, i1, i2), f_d = (i_d + 0.5) / n_d (a division),
+ * c_e = ((f0 * box[0][e] + f1 * box[1][e]) + f2 * box[2][e]) + origin[e], uncontracted: ((argwhere + 0.5) / ncell) @ box + origin,
+ * the centre of an EQUAL-width cell; cell (cap) i32, optional: its flat index.  More empty cells than cap: MDH_ERR_ARG, the count
+ * still delivered.  cx == cy == cz == cell == NULL: the count alone.  Waits for the stream (the count is read back). */
+int mdh_void_points(const int *cells, int n0, int n1, int n2, const double *box9, const double *origin3, double *cx, double *cy, double *cz,
+                    int *cell, int64_t cap, int64_t *count_host, int space, void *stream);
+/* After the points have been clustered (mdh_cluster: cluster_id (M) i32 in 1 .. cluster_number): the points of the clusters of
+ * more than one point, in the order they had, into ox, oy, oz (M) f64 and new_id (M) i32 — the surviving clusters renumbered
+ * 1 .. *void_number_host in ascending old id; *kept_host = how many points were written (the entries behind them are not touched).
+ * An id outside 1 .. cluster_number belongs to no cluster and is dropped.  Waits for the stream. */
+int mdh_void_prune(const double *x, const double *y, const double *z, const int *cluster_id, int64_t M, int cluster_number, double *ox,
+                   double *oy, double *oz, int *new_id, int64_t *kept_host, int *void_number_host, int space, void *stream);
+
 /* ---- _repeat_cell ----------------------------------------------------- */
 /* replaces _repeat_cell.repeat_cell                        src/repeat_cell.cpp:19-61; new_pos flat (n_old*nx*ny*nz*3) */
 int mdh_repeat_cell(double *new_pos, const double *old_box9_host, const double *old_pos, int64_t n_old, int nx,

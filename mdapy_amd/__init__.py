@@ -20,6 +20,7 @@ from .chill_plus import ChillPlus
 from .wigner_seitz_defect import WignerSeitzAnalysis
 from .lindemann_parameter import LindemannParameter
 from .mean_squared_displacement import MeanSquaredDisplacement
+from .void_analysis import VoidAnalysis
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -27,6 +28,6 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement",
+    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

@@ -1,6 +1,7 @@
 """Drop-in for the reference's ``mdapy._neighbor`` nanobind module
 (src/neighbor.cpp:841-859): same function names, argument order and
-caller-allocated outputs, executed by the HIP kernels in csrc/neighbor.hip and csrc/rows.hip (the cell grid under them: csrc/cell_grid.hip).
+caller-allocated outputs, executed by the HIP kernels in csrc/neighbor.hip and csrc/rows.hip (the cell grid under them: csrc/cell_grid.hip;
+``_fill_cell_for_void``: csrc/voids.hip).
 Arrays may be numpy (host; staged by the library) or HBM resident
 (:class:`mdapy_amd.devarray.HArray`, frame columns, torch ROCm tensors)."""
 import numpy as np
@@ -171,3 +172,23 @@ def filter_overlap_atom_with_grain(x, y, z, type_list, grain_id, box, origin, bo
                                                              pb, po, pp, float(rc_metal_metal), float(rc_cc), float(rc_metal_c),
                                                              out.ctypes.data, _lib.HOST, None))
     return out.astype(bool)
+
+
+def _fill_cell_for_void(x, y, z, box, origin, boundary, rc, num_t=1):
+    """src/neighbor.cpp:780 — the (ncell0, ncell1, ncell2) int32 grid of the cutoff build's cells, ncell = max(floor(thickness /
+    rc), 3): 1 where at least one atom falls, 0 elsewhere.  A numpy array for numpy positions, HBM resident otherwise.
+    ``rc <= 0``, a singular box and a grid of more cells than int32 indexes raise ``ValueError``."""
+    import ctypes
+
+    keep, (pb, po, pp) = _lib.host_box(box, origin, boundary)
+    n = int(len(x))
+    _lib.same_rows("_fill_cell_for_void", n, y=y, z=z)
+    dims = (ctypes.c_int * 3)()
+    _lib.check(_lib.lib().mdh_void_grid_dims(pb, po, pp, float(rc), ctypes.addressof(dims)))
+    shape = tuple(int(d) for d in dims)
+    c = Call(x, y, z)
+    cells = HArray.empty(shape, i32) if c.space == _lib.DEVICE else np.empty(shape, i32)
+    rc_ = _lib.lib().mdh_fill_cell_for_void(c.inp(x, f64), c.inp(y, f64), c.inp(z, f64), n, pb, po, pp, float(rc),
+                                            c.out(cells, i32, upload=False), shape[0] * shape[1] * shape[2], c.space, c.stream)
+    c.done(rc_)
+    return cells

@@ -33,6 +33,9 @@ from . import _sfc as sfc
 # (not in NAMES either: the oracle has no atomic strain; its tests install a restatement as kernels.strain)
 from . import _strain as strain
 from . import _structure_entropy as structure_entropy
+# (not in NAMES either: the oracle has no adapter for the void analysis; its tests install a restatement as kernels.void and as
+# kernels.neighbor._fill_cell_for_void)
+from . import _void as void
 from . import _voronoi as voronoi
 from . import _wcp as wcp
 
