@@ -567,6 +567,35 @@ int mdh_msd_window(const double *pos, int64_t F, int64_t N, int64_t L, double *p
 /* direct: particle_msd (F, N) f64: [t, i] = term(pos[t, i], pos[0, i]); msd (F) f64 as above */
 int mdh_msd_direct(const double *pos, int64_t F, int64_t N, double *particle_msd, double *msd, int space, void *stream);
 
+/* ---- _unwrap ----------------------------------------------------------- */
+/* A wrapped trajectory made continuous across its periodic boundaries: what _lindemann and _msd above want as input.  The
+ * reference has no compiled module for this (src/mdapy/unwrap_trajectory.py:212-255 walks the frames in numpy).  Every operation
+ * is IEEE binary64 without contraction, in this order, inv[f] being the inverse of frame f's own cell:
+ *   frac[f, i, d] = (x * inv[f][0][d] + y * inv[f][1][d]) + z * inv[f][2][d]
+ *   minimum-image mode (image == NULL): k[f, i, d] = rint(frac[f-1, i, d] - frac[f, i, d]) (ties to even) for f >= 1 on the axes
+ *     with pbc3_host[d] != 0, else 0; s[f, i, :] = the sum of k[g, i, :] over g <= f, in int64
+ *   image mode: s[f, i, :] = image[f, i, :] on all three axes, whatever pbc3_host says; inv_host is not read
+ *   unwrapped[f, i, d] = p_d + (((double)sx * cell[f][0][d] + (double)sy * cell[f][1][d]) + (double)sz * cell[f][2][d])
+ * with (x, y, z) = p = pos[f, row_of[f, i]] (pos[f, i] without row_of): the gather happens on the read side, no sorted copy of the
+ * trajectory exists.  chunks: the frames are cut into this many runs, each walked by its own waves (their sums are joined by a
+ * scan over the runs; the positions are then read twice); 0 = the library chooses (one run when ceil(N / 64) >= 2 048, or >= 1 024 with
+ * row_of, else enough for 4 096 waves and at most ceil(F / 16): profiles/unwrap.md); always clamped to F.  The sums are integers: every chunk count gives the same bits.
+ * Scratch: chunks x N x 3 int64 when chunks > 1 in minimum-image mode.
+ * F < 1, N < 1, chunks < 0, a NULL pos / cell_host / pbc3_host / unwrapped, or a NULL inv_host in minimum-image mode return
+ * MDH_ERR_ARG before any device work, as do F > 2^24, N > 2^28 and ceil(N / 64) x chunks > 2^31 - 1.  A step frac[f-1] - frac[f]
+ * that is not finite or whose magnitude is >= 2^31 (a NaN position, a degenerate cell) and a row_of entry outside [0, N) are
+ * never used: the kernel raises a bit of a flag word in device memory, which is read back after the last kernel, and the call
+ * returns MDH_ERR_ARG (the outputs then hold no result).  For that read the call synchronises the stream. */
+int mdh_unwrap_trajectory(const double *pos,       /* (F, N, 3) f64, C-contiguous, wrapped positions */
+                          const int64_t *row_of,   /* (F, N) or NULL: output row i of frame f is input row row_of[f, i] */
+                          const int32_t *image,    /* (F, N, 3) or NULL: ix iy iz, indexed like pos (through row_of) */
+                          const double *cell_host, /* (F, 3, 3) rows a, b, c of every frame, host memory */
+                          const double *inv_host,  /* (F, 3, 3) their inverses, host memory; unused when image != NULL */
+                          const int *pbc3_host, int64_t F, int64_t N, int chunks,
+                          double *unwrapped,       /* (F, N, 3) f64 */
+                          int64_t *shifts,         /* (F, N, 3) or NULL: the integer shift applied to every atom and frame */
+                          int space, void *stream);
+
 /* ---- void analysis ------------------------------------------------------ */
 /* replaces _neighbor._fill_cell_for_void (src/neighbor.cpp:780-839) and keeps the rest of mdapy.VoidAnalysis
  * (src/mdapy/void_analysis.py) on the device.  The grid is the cutoff neighbour build's: ncell[d] = max(floor(thickness[d] / rc), 3)

@@ -21,6 +21,8 @@ from .wigner_seitz_defect import WignerSeitzAnalysis
 from .lindemann_parameter import LindemannParameter
 from .mean_squared_displacement import MeanSquaredDisplacement
 from .void_analysis import VoidAnalysis
+from .trajectory import Trajectory
+from .unwrap_trajectory import unwrap_trajectory
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -29,5 +31,6 @@ __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
     "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
+    "Trajectory", "unwrap_trajectory",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

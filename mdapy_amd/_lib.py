@@ -114,6 +114,7 @@ _SIGNATURES = {
     "mdh_lindemann_all": [vp, i64, i64, vp, vp, vp, vp, cint, cint, vp],
     "mdh_msd_window": [vp, i64, i64, i64, vp, vp, cint, vp],
     "mdh_msd_direct": [vp, i64, i64, vp, vp, cint, vp],
+    "mdh_unwrap_trajectory": [vp, vp, vp, vp, vp, vp, i64, i64, cint, vp, vp, cint, vp],
     "mdh_void_grid_dims": [vp, vp, vp, dbl, vp],
     "mdh_fill_cell_for_void": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, i64, cint, vp],
     "mdh_void_points": [vp, cint, cint, cint, vp, vp, vp, vp, vp, vp, i64, vp, cint, vp],

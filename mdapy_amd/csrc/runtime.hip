@@ -399,6 +399,7 @@ void warm_knn(hipStream_t st);
 void warm_wigner_seitz(hipStream_t st);
 void warm_lindemann(hipStream_t st);
 void warm_msd(hipStream_t st);
+void warm_unwrap(hipStream_t st);
 void warm_voids(hipStream_t st);
 void warm_repeat(hipStream_t st);
 void warm_ptm(hipStream_t st);
@@ -526,6 +527,7 @@ int mdh_warm(void)
     mdh::warm_wigner_seitz(nullptr);
     mdh::warm_lindemann(nullptr);
     mdh::warm_msd(nullptr);
+    mdh::warm_unwrap(nullptr);
     mdh::warm_voids(nullptr);
     mdh::warm_repeat(nullptr);
     mdh::warm_ptm(nullptr);

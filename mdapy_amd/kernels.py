@@ -33,6 +33,8 @@ from . import _sfc as sfc
 # (not in NAMES either: the oracle has no atomic strain; its tests install a restatement as kernels.strain)
 from . import _strain as strain
 from . import _structure_entropy as structure_entropy
+# (not in NAMES either: neither the reference nor the oracle has a compiled unwrap; its tests install a restatement as kernels.unwrap)
+from . import _unwrap as unwrap
 # (not in NAMES either: the oracle has no adapter for the void analysis; its tests install a restatement as kernels.void and as
 # kernels.neighbor._fill_cell_for_void)
 from . import _void as void

@@ -60,33 +60,70 @@ def _table_on_host(body: bytes, nrows: int, names: List[str], kinds: List[int], 
     return out
 
 
-def _table(path, offset: int, nrows: int, names: List[str], kinds: List[int]):
-    """columns of the table that starts `offset` bytes into the (decompressed) file; (columns, lines present or None)"""
-    size = None if str(path).endswith(".gz") else os.path.getsize(path) - offset
+class _UpTo:
+    """the next ``left`` bytes of a binary file, as the file object ``_text.stream_to_device`` reads from"""
+
+    def __init__(self, f, left: int):
+        self._f, self._left = f, left
+
+    def readinto(self, view):
+        if self._left <= 0:
+            return 0
+        got = self._f.readinto(view[: self._left] if len(view) > self._left else view)
+        self._left -= got or 0
+        return got
+
+
+class _At:
+    """``source`` positioned ``offset`` bytes into its (decompressed) content.  A source is a path, opened here and closed
+    again, or a binary file that is open already: a trajectory reads all its frames through one handle, front to back, so that a
+    compressed file is inflated once."""
+
+    def __init__(self, source, offset: int):
+        self._source, self._offset, self._mine = source, offset, None
+
+    def __enter__(self):
+        f = self._source
+        if isinstance(f, str):
+            f = self._mine = _open(f)
+        f.seek(self._offset)
+        return f
+
+    def __exit__(self, *exc):
+        if self._mine is not None:
+            self._mine.close()
+
+
+def _name(source) -> str:
+    return source if isinstance(source, str) else str(getattr(source, "name", source))
+
+
+def _table(source, offset: int, nrows: int, names: List[str], kinds: List[int], end: Optional[int] = None):
+    """columns of the table in bytes ``offset .. end`` of the (decompressed) source, ``end`` None: up to the end of the file;
+    (columns, lines present or None)"""
+    if end is not None:
+        size = end - offset
+    else:
+        size = None if _name(source).endswith(".gz") else os.path.getsize(_name(source)) - offset
     if have_gpu() and nrows > 0 and (size is None or size >= DEVICE_MIN_BYTES):
         from . import _text
 
-        with _open(path) as f:
-            if size is None:
-                f.read(offset)
-            else:
-                f.seek(offset)
-            text, _ = _text.stream_to_device(f, size)
+        with _At(source, offset) as f:
+            text, _ = _text.stream_to_device(f if end is None else _UpTo(f, size), size)
         try:
             cols, lines = _text.parse_table(text, nrows, kinds)
             return dict(zip(names, cols)), lines
         except _text.RedoOverflow:  # e.g. a column of strings longer than 8 bytes on every atom: the host tokenizer reads it
             del text
-    with _open(path) as f:
-        f.read(offset) if size is None else f.seek(offset)
-        body = f.read()
-    return _table_on_host(body, nrows, names, kinds, str(path)), None
+    with _At(source, offset) as f:
+        body = f.read() if end is None else f.read(size)
+    return _table_on_host(body, nrows, names, kinds, _name(source)), None
 
 
-def _header(path, nlines: int) -> Tuple[List[str], int]:
-    """the first nlines lines (decoded, without line ends) and the byte offset of what follows"""
-    out, offset = [], 0
-    with _open(path) as f:
+def _header(source, nlines: int, start: int = 0) -> Tuple[List[str], int]:
+    """the first nlines lines from byte ``start`` on (decoded, without line ends) and the byte offset of what follows"""
+    out, offset = [], start
+    with _At(source, start) as f:
         for _ in range(nlines):
             ln = f.readline()
             if not ln:
@@ -131,9 +168,10 @@ def _dump_box(bounds_line: str, rows: List[List[str]]):
     return np.array([[xhi - xlo, 0, 0], [0, yhi - ylo, 0], [0, 0, zhi - zlo], [xlo, ylo, zlo]], dtype=np.float64), boundary
 
 
-def read_dump(path) -> Tuple[Frame, Box, Dict[str, Any]]:
-    path = str(path)
-    head, offset = _header(path, 9)
+def _dump_frame(source, head: List[str], offset: int, end: Optional[int] = None, what: Optional[str] = None):
+    """one dump frame -> (Frame, Box, info): ``head`` its nine header lines, its table the bytes ``offset .. end`` of the source
+    (``end`` None: the single-frame reader, whose table runs to the end of the file and must not be followed by another frame)"""
+    path = what or _name(source)
     if len(head) < 9:
         raise ValueError(f"{path}: dump frame has only {len(head)} lines (<9)")
     if not head[0].strip().startswith("ITEM: TIMESTEP"):
@@ -153,8 +191,8 @@ def read_dump(path) -> Tuple[Frame, Box, Dict[str, Any]]:
         raise ValueError(f"{path}: expected 'ITEM: ATOMS' on line 9")
     names = head[8].split()[2:]
     kinds = [INT if nm in _INT_COLUMNS else STR if nm in _STR_COLUMNS else FLOAT for nm in names]
-    cols, lines = _table(path, offset, n, names, kinds)
-    if (lines is None or lines > n) and _has_second_frame(path, offset):  # rows beyond the frame: is it another frame?
+    cols, lines = _table(source, offset, n, names, kinds, end)
+    if end is None and (lines is None or lines > n) and _has_second_frame(source, offset):  # rows beyond the frame: is it another frame?
         raise ValueError(f"{path}: multi-frame dump file. Use a trajectory reader or split the file first.")
     have = set(cols)
     if not {"x", "y", "z"} <= have:  # load_save.py:182-196
@@ -173,10 +211,15 @@ def read_dump(path) -> Tuple[Frame, Box, Dict[str, Any]]:
     return _frame(cols), Box(box[:3], boundary, box[3]), {"timestep": timestep}
 
 
+def read_dump(path) -> Tuple[Frame, Box, Dict[str, Any]]:
+    path = str(path)
+    head, offset = _header(path, 9)
+    return _dump_frame(path, head, offset)
+
+
 def _has_second_frame(path, offset: int) -> bool:
     needle = b"ITEM: TIMESTEP"
-    with _open(path) as f:
-        f.read(offset) if str(path).endswith(".gz") else f.seek(offset)
+    with _At(path, offset) as f:
         carry = b""
         while True:
             chunk = f.read(1 << 24)
@@ -225,9 +268,10 @@ def _xyz_columns(properties: str, source: str) -> Tuple[List[str], List[int]]:
     return names, kinds
 
 
-def read_xyz(path) -> Tuple[Frame, Box, Dict[str, Any]]:
-    path = str(path)
-    head, offset = _header(path, 2)
+def _xyz_frame(source, head: List[str], offset: int, end: Optional[int] = None, what: Optional[str] = None):
+    """one XYZ frame -> (Frame, Box, info): ``head`` its count and comment lines, its table the bytes ``offset .. end`` of the
+    source (``end`` None: to the end of the file)"""
+    path = what or _name(source)
     if len(head) < 2:
         raise ValueError(f"{path}: too short to be an XYZ file")
     n = int(head[0].strip())
@@ -248,7 +292,7 @@ def read_xyz(path) -> Tuple[Frame, Box, Dict[str, Any]]:
     else:
         boundary = [0, 0, 0] if classical else [1, 1, 1]
     origin = np.array(info["origin"].split(), dtype=np.float64) if "origin" in info else np.zeros(3)
-    cols, lines = _table(path, offset, n, names, kinds)
+    cols, lines = _table(source, offset, n, names, kinds, end)
     if lines is not None and lines < n:
         raise ValueError(f"{path}: header says {n} atoms but only {lines} body lines present")
     if classical:
@@ -261,6 +305,12 @@ def read_xyz(path) -> Tuple[Frame, Box, Dict[str, Any]]:
     for key in ("pbc", "properties", "origin", "lattice"):
         info.pop(key, None)
     return _frame(cols), Box(cell, boundary, origin), info
+
+
+def read_xyz(path) -> Tuple[Frame, Box, Dict[str, Any]]:
+    path = str(path)
+    head, offset = _header(path, 2)
+    return _xyz_frame(path, head, offset)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
