@@ -420,8 +420,8 @@ __device__ __forceinline__ void sort_cell_net(int *__restrict__ order, int s, in
 // per cell, up to 50 in the fat last cells: 239 -> 204 us at 10 M atoms, 131 -> 94 us at 3.4 M)
 // A cell of more than SLOT_CAP atoms, seen by the in-cell sort of a build whose signature may take the slot grid next time: the
 // build's generation is stamped into ctl[3] (once per build or nearly: the others find the stamp in L2 and leave) and the cell's
-// count goes to the signature's pinned words (SlotHistory::host[1]).  The last kernel of the pass over the grid publishes the
-// stamp as host[0] = 1 or 0 (CellGrid::big_sink).
+// count goes to the signature's record (GridFeedback::BIG + 1).  The last kernel of the pass over the grid publishes the
+// stamp as its word BIG = 1 or 0 (CellGrid::big_sink).
 __device__ __forceinline__ void report_big_cell(unsigned *__restrict__ ctl, unsigned gen, int *__restrict__ sink, int n)
 {
     if (__hip_atomic_load(&ctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen)
@@ -770,40 +770,41 @@ static std::atomic<int> g_slot_grid{[] { const char *e = std::getenv("MDH_SLOT_G
 static const bool g_slot_force = [] { const char *e = std::getenv("MDH_SLOT_GRID_FORCE"); return e && std::atoi(e) != 0; }();
 static std::atomic<int> g_last_slot_build{0}; // the last FOR_ROWS build of the process was a slot build (mdh_debug_neighbor_plan)
 int last_grid_was_slot() { return g_last_slot_build.load(std::memory_order_relaxed); }
-static std::mutex g_slot_mu;
-// per (N, grid, device): two pinned words the device writes: host[0] = did the last FINISHED build of the signature see a cell of more
-// than SLOT_CAP atoms (1 / 0; -1: none has finished yet — the first builds of a signature are compact ones), host[1] = such a cell's count
-struct SlotHistory { int64_t N, ncell; int device; int *host; };
+static std::mutex g_slot_mu; // the two tables below: their lookups and hand-overs only, never across a launch, a copy or a wait
 // per KEEP_SLOT block: the half the next slot build counts into (all zero) and the words of each half that are not zero
 struct SlotBlock { void *p; int next; int64_t dirty[2]; };
-static std::vector<SlotHistory *> g_slot_hist;
-static std::atomic<SlotHistory *> g_last_hist{nullptr}; // the signature of the last build that kept a history (mdh_debug_slot_grid_counters)
+static std::vector<GridFeedback *> g_feedback; // per (N, grid, device), grid.hpp: at most 64, the oldest first
+static std::atomic<GridFeedback *> g_last_hist{nullptr}; // the signature of the last build that kept a history (mdh_debug_slot_grid_counters)
 static std::vector<SlotBlock *> g_slot_blocks;
 
-static int slot_history(int64_t N, int64_t ncell, SlotHistory **out)
+// the signature's record, made on first sight with nothing known.  (Two threads that meet the same fresh signature get the same
+// record and may both count its statistics into it, grid_stats_hint: the same numbers twice.)
+static int grid_feedback(int64_t N, int64_t ncell, GridFeedback **out)
 {
     int device = 0;
     (void)hipGetDevice(&device);
     std::lock_guard<std::mutex> lk(g_slot_mu);
-    for (SlotHistory *h : g_slot_hist)
-        if (h->N == N && h->ncell == ncell && h->device == device) { *out = h; return MDH_OK; }
-    SlotHistory *h = nullptr;
-    if (g_slot_hist.size() >= 64) {
-        // the oldest signature hands its entry and its pinned words on (grid_stats_hint does the same).  A build of that old signature
-        // may still be in flight and write its answer into them: the new signature then reads a wrong history once, which picks a
-        // path, never a result
-        h = g_slot_hist.front();
-        g_slot_hist.erase(g_slot_hist.begin());
+    for (GridFeedback *f : g_feedback)
+        if (f->N == N && f->ncell == ncell && f->device == device) { *out = f; return MDH_OK; }
+    GridFeedback *f = nullptr;
+    if (g_feedback.size() >= 64) {
+        // the oldest signature hands its record and its pinned block on.  A build of that old signature may still be in flight and
+        // write its answers into them (a copy enqueued on some other stream may still land, too): the new signature then reads a
+        // wrong hint or a wrong history once, which picks a path, never a result
+        f = g_feedback.front();
+        g_feedback.erase(g_feedback.begin());
     } else {
         int *host = nullptr;
-        MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&host), 2 * sizeof(int), hipHostMallocDefault));
-        h = new SlotHistory{};
-        h->host = host;
+        MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&host), GridFeedback::WORDS * sizeof(int), hipHostMallocDefault));
+        f = new GridFeedback{};
+        f->host = host;
     }
-    h->N = N; h->ncell = ncell; h->device = device;
-    h->host[0] = -1; h->host[1] = 0;
-    g_slot_hist.push_back(h);
-    *out = h;
+    f->N = N; f->ncell = ncell; f->device = device;
+    std::fill(f->host, f->host + GridFeedback::WORDS, 0);
+    f->host[GridFeedback::LISTED] = f->host[GridFeedback::BIG] = -1;
+    f->width = 0; f->calls = 0;
+    g_feedback.push_back(f);
+    *out = f;
     return MDH_OK;
 }
 static SlotBlock *slot_block_state(void *p)
@@ -843,6 +844,10 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
     cg.imv = nullptr;
     cg.slot_cap = 0; cg.spill = nullptr; cg.n_spill = nullptr; cg.n_binned = N;
     cg.big_stamp = nullptr; cg.big_gen = 0; cg.big_sink = nullptr;
+    // a build for rows: the one lookup of the signature's record; the passes over the grid reach it through cg.fb
+    cg.fb = nullptr;
+    if (packed && rq.slots_ok) MDH_TRY(grid_feedback(N, g.ncell, &cg.fb));
+    const int row_width = rq.row_width < 0 ? (cg.fb ? cg.fb->width.load(std::memory_order_relaxed) : 0) : rq.row_width;
     // what the atoms are wanted as — decided before anything is allocated: a slot grid has no entries, no prefix array and
     // counters of its own
     // scattered (FOR_ROWS_UNORDERED): the caller knows that the atoms come in no spatial order
@@ -859,22 +864,22 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
         // mdh_debug_set_indirect(0): the records always — an A/B switch, and how the tests reach both paths on one input
         // (not for dense cells — six atoms and more, the wide instance's ground: two workgroups per CU hide the staging's
         // dependent gathers badly, build_neighbor(5.0, 50) at 10 M atoms 4.48 -> 4.60 ms; profiles/r06_cell_grid_ab.txt)
-        indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && rq.sort_desc && (double)N <= 6.0 * (double)g.ncell && rq.row_width <= 16;
+        indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && rq.sort_desc && (double)N <= 6.0 * (double)g.ncell && row_width <= 16;
     }
     // The slot grid (CellGrid::slot_cap) where the rule allows.  What the rule asks of the signature's history comes from two
-    // pinned words: the in-cell sort of every build that could have been a slot build stamps one with its generation when it sees a
-    // cell of more than SLOT_CAP atoms, and the tile kernel's mop-up reports the tiles it was left (lane_listed_hint).  Both arrive
-    // when the device gets there: a build that reads an old answer is a slower one, never a wrong one.
-    SlotHistory *hist = nullptr;
+    // pinned words of its record: the in-cell sort of every build that could have been a slot build stamps one with its generation
+    // when it sees a cell of more than SLOT_CAP atoms (GridFeedback::BIG), and the tile kernel's mop-up reports the tiles it was left
+    // (GridFeedback::LISTED).  Both arrive when the device gets there: a build that reads an old answer is a slower one, never a wrong one.
+    int *hist = nullptr; // != nullptr: this build keeps the history (the record's two words from BIG on)
     bool slot = false;
     const bool windows = window.set || centre.set;
-    if (packed && rq.slots_ok && slot_grid_rule(indirect, rq.sort_key != nullptr, windows, rq.row_width, g.ncell, N, true, false, 0)) {
-        MDH_TRY(slot_history(N, g.ncell, &hist));
-        g_last_hist.store(hist, std::memory_order_relaxed);
-        const int last = *(volatile int *)hist->host;
+    if (cg.fb && slot_grid_rule(indirect, rq.sort_key != nullptr, windows, row_width, g.ncell, N, true, false, 0)) {
+        hist = cg.fb->host + GridFeedback::BIG;
+        g_last_hist.store(cg.fb, std::memory_order_relaxed);
+        const int last = *(volatile int *)hist, listed = ((volatile int *)cg.fb->host)[GridFeedback::LISTED];
         const bool seen = last >= 0, big = last > 0;
         slot = g_slot_grid.load(std::memory_order_relaxed) != 0 && (g_slot_force ||
-               slot_grid_rule(indirect, rq.sort_key != nullptr, windows, rq.row_width, g.ncell, N, seen, big, lane_listed_hint(N, g.ncell)));
+               slot_grid_rule(indirect, rq.sort_key != nullptr, windows, row_width, g.ncell, N, seen, big, listed));
     }
     // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
     // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
@@ -983,7 +988,7 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
         if (b.tri) { if (assign4) MDH_ASSIGN_SLOT(true, 4); else MDH_ASSIGN_SLOT(true, 1); }
         else { if (assign4) MDH_ASSIGN_SLOT(false, 4); else MDH_ASSIGN_SLOT(false, 1); }
         hipLaunchKernelGGL(k_sort_slots, dim3(grid_for(std::max<int64_t>(g.ncell, slot_idle_n), 256)), dim3(256), 0, st, cell_count, cg.order, g.ncell,
-                           slot_idle, slot_idle_n, ctl, gen, hist->host, cg.flags, slot_hi);
+                           slot_idle, slot_idle_n, ctl, gen, hist, cg.flags, slot_hi);
         MDH_HIP(hipGetLastError());
         {
             std::lock_guard<std::mutex> lk(g_slot_mu);
@@ -992,7 +997,7 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
             sb->next = 1 - sb->next;
         }
         sc.keep_confirm(slot_block);
-        cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist->host;
+        cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist;
         cg.slot_cap = SLOT_CAP;
         cg.slot_hi = slot_hi;
         cg.spill = ent;
@@ -1052,9 +1057,8 @@ int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z
             hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rank);
         } else if (!windowed) {
             // (hist: this build could have been a slot build — it reports a cell of more than SLOT_CAP atoms as one would)
-            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rq.sort_key, rank, ctl, gen,
-                               hist ? hist->host : (int *)nullptr);
-            if (hist) { cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist->host; }
+            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rq.sort_key, rank, ctl, gen, hist);
+            if (hist) { cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist; }
         } else {
             hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p1 - p0) * plane, 256)), dim3(256), 0, st, cg.cell_start + p0 * plane, cg.order, (p1 - p0) * plane, rq.sort_key, rank);
             if (p3 > p2)
@@ -1106,14 +1110,15 @@ int mdh_debug_set_slot_grid(int on)
 {
     if (on == 2) { // ... and every signature's history forgotten: its next build is a first one
         std::lock_guard<std::mutex> lk(g_slot_mu);
-        for (SlotHistory *h : g_slot_hist) h->host[0] = -1; // (the caller has synchronised: no build is in flight)
+        for (GridFeedback *f : g_feedback) f->host[GridFeedback::BIG] = -1; // (the caller has synchronised: no build is in flight)
     }
     return g_slot_grid.exchange(on ? 1 : 0);
 }
 int mdh_debug_slot_grid_counters(int64_t *out4)
 {
-    const SlotHistory *h = g_last_hist.load(std::memory_order_relaxed);
-    const int last = h ? ((const volatile int *)h->host)[0] : 0, big = h ? ((const volatile int *)h->host)[1] : 0;
+    const GridFeedback *f = g_last_hist.load(std::memory_order_relaxed);
+    const volatile int *h = f ? f->host + GridFeedback::BIG : nullptr;
+    const int last = h ? h[0] : 0, big = h ? h[1] : 0;
     out4[0] = last_grid_was_slot();
     out4[1] = last > 0 ? 1 : 0;
     out4[2] = out4[1] ? big : 0;

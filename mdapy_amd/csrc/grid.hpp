@@ -1,6 +1,7 @@
 // grid.hpp — the rc-wide cell grid shared by the neighbor build, kNN and RDF kernels.
 #pragma once
 #include "common.hpp"
+#include <atomic>
 #include <cmath>
 
 namespace mdh {
@@ -33,9 +34,11 @@ __host__ __device__ __forceinline__ int combine(int cc, int ca)
 __host__ __device__ __forceinline__ int axis(int code, int d) { return ((code >> (5 * d)) & 31) - 16; } // image number of a combined code
 } // namespace img
 
+struct GridFeedback;
 // device buffers produced by build_cell_grid, cell_grid.hip (owned by the Scope that built them)
 struct CellGrid {
     Grid g;
+    GridFeedback *fb = nullptr; // a build for neighbor rows (GridRequest::slots_ok): what the builds of its signature leave for the next one
     int win_lo = 0, win_hi = 0; // planes [win_lo, win_hi) of axis 0 the grid was built over (a promised window, cell_grid.hip); 0, 0: all
     int cen_lo = 0, cen_hi = 0; // planes [cen_lo, cen_hi) of axis 0 whose atoms want rows (mdh_hint_centre_window: a slab's own atoms; the rest of the window is halo); 0, 0: all
     mutable bool flags_fresh = false; // flags[] were zeroed by build_cell_grid and nobody has used them yet (the first neighbor pass skips its own memset: every hipMemsetAsync is a 5 us launch)
@@ -69,7 +72,7 @@ struct CellGrid {
     const int2 *spill = nullptr;      // [N]
     const unsigned *n_spill = nullptr; // device counter: entries of spill
     int64_t n_binned = 0;             // slot grid: atoms handed to the build (absent ones, x = NaN, included: they take no cell)
-    // a build that keeps the slot grid's history (cell_grid.hip SlotHistory): its in-cell sort stamps *big_stamp with big_gen when it sees
+    // a build that keeps the slot grid's history (GridFeedback::BIG): its in-cell sort stamps *big_stamp with big_gen when it sees
     // a cell of more than SLOT_CAP atoms; the LAST kernel of the pass over the grid turns that into the signature's pinned word
     // (TileFilter::big_sink: 1 or 0 — a definite answer per finished build, so a host that runs many builds ahead reads the last one)
     const unsigned *big_stamp = nullptr;
@@ -143,9 +146,8 @@ struct TileFilter {
     int *listed_sink = nullptr; // != nullptr: the list is the tile kernel's FIRST pass's (no slice pass ran); the mop-up writes its length here (GridStats::listed_sink)
     const unsigned *big_stamp = nullptr; unsigned big_gen = 0; int *big_sink = nullptr; // CellGrid::big_sink: published by the pass's last kernel
 };
-// occupied_cells: cells that hold atoms (occupied_cells_hint); 0 = assume all of them
+// occupied_cells: cells of the occupied region (GridStats::v[0]); 0 = assume all of them
 TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells);
-int occupied_cells_hint(Scope &sc, const CellGrid &cg, int64_t N, int64_t *occupied);
 
 // What one pass over a built cell grid is to leave behind (neighbor.hip neighbor_pass and the kernels' launchers)
 struct RowsRequest {
@@ -187,9 +189,25 @@ struct LanePlan {
     bool full;        // every 4x4x4 block of cells holds atoms (last known statistics): all tiles are live
     int64_t occupied; // cells of the occupied region (last known)
 };
-int grid_stats_hint(Scope &sc, const CellGrid &cg, int64_t N, GridStats *out);
+// What the builds of one (N, grid, device) signature leave for the next one: a neighbor build steers itself by what the previous
+// build of the same system reported.  One heap object per signature, never freed (cell_grid.hip grid_feedback), reached through
+// CellGrid::fb.  Every word arrives when the device gets there: a build that reads an old answer is a slower one, never a wrong one.
+struct GridFeedback {
+    static constexpr int LISTED = GridStats::NBIN, BIG = LISTED + 1, WORDS = BIG + 2;
+    int64_t N, ncell; int device; // the signature
+    // one block of pinned host memory that the device writes:
+    //   [0, NBIN)  GridStats::v, copied behind k_grid_stats (grid_stats_hint)
+    //   [LISTED]   tiles the first pass of the last finished build listed for the second (-1: not known; GridStats::listed_sink)
+    //   [BIG]      did the last FINISHED build see a cell of more than SLOT_CAP atoms (1 / 0; -1: none has finished yet — the first
+    //              builds of a signature are compact ones; CellGrid::big_sink), [BIG + 1] such a cell's count
+    int *host;
+    // host only (atomic: two threads may build the same signature)
+    std::atomic<int> width;      // the last exact row width (mdh_build_neighbor_exact); 0: none
+    std::atomic<unsigned> calls; // builds that have read the statistics; 0: not counted yet
+};
+// the statistics of cg's signature (cg.fb), counted on the device when they are stale
+int grid_stats_hint(Scope &sc, const CellGrid &cg, GridStats *out);
 LanePlan plan_lane(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count);
-int lane_listed_hint(int64_t N, int64_t ncell); // tiles the last finished build of this (N, grid) listed; -1: not known (cell_grid.hip: the slot grid's taking rule)
 int lane_last_listed(); // tiles listed for the slice pass as last seen when a plan was made (mdh_debug_counters)
 int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, int64_t N, const DBox &b, double rc,
                          const RowsRequest &rows, TileFilter &tf);
@@ -370,7 +388,7 @@ struct GridRequest {
     bool sort_desc = false;  // every cell's atoms by descending id (reference row order); else as the atomic counters placed them
     const int64_t *sort_key = nullptr; // [N] descending key[id] instead of descending id
     Atoms atoms = SORTED_ARRAYS;
-    // FOR_ROWS: width of the rows about to be built (0: not known, or counting).  Rows of more than 16 slots go to the tile kernel's
+    // FOR_ROWS: width of the rows about to be built (0: not known, or counting; < 0: the signature's last exact width, GridFeedback::width).  Rows of more than 16 slots go to the tile kernel's
     // wide instance, which hides the indirect staging's gathers badly (two or three workgroups per CU): such a build keeps the
     // records (the 12-nearest search's cutoff build, 4.7 atoms per cell, rows of 24: 2.15 ms with records, 2.22 without)
     int row_width = 0;

@@ -9,8 +9,6 @@
 #include "grid.hpp"
 #include "cna_core.hpp"
 #include <algorithm>
-#include <mutex>
-#include <vector>
 
 namespace mdh {
 
@@ -285,25 +283,6 @@ __global__ __launch_bounds__(256) void k_max_i32(const int *__restrict__ v, int6
     raise_max(out, wave_max(m));
 }
 
-// last exact row width seen for a (N, grid) signature; set < 0: query only
-static int width_hint(int64_t N, int64_t ncell, int set)
-{
-    struct Entry { int64_t N, ncell; int width; };
-    static std::mutex mu;
-    static std::vector<Entry> table;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto &e : table)
-        if (e.N == N && e.ncell == ncell) {
-            if (set >= 0) e.width = set;
-            return e.width;
-        }
-    if (set > 0) {
-        if (table.size() >= 64) table.erase(table.begin());
-        table.push_back(Entry{N, ncell, set});
-    }
-    return 0;
-}
-
 // One pass over a built cell grid (RowsRequest, grid.hpp).  The tile kernel where it applies, the round-1 tiled kernel for cells
 // too full for it, the thread-per-atom code for the rest.
 // labelled: the request's fixed-cutoff CNA labels were written by the tile kernel (the leftovers of its mop-up kernels are listed in
@@ -319,9 +298,9 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
     TileFilter tf{};
     tf.big_stamp = cg.big_stamp; tf.big_gen = cg.big_gen; tf.big_sink = cg.big_sink;
     bool done = false;
+    GridStats gs; // both planners size their tiles by the signature's statistics
+    if (g_neighbor_variant != 1) MDH_TRY(grid_stats_hint(sc, cg, &gs));
     if (g_neighbor_variant == 0) { // tile kernel (orthogonal and triclinic boxes); the thread-per-atom code below then only mops up what it listed
-        GridStats gs;
-        MDH_TRY(grid_stats_hint(sc, cg, N, &gs));
         const bool cna = rows.pattern && !count;
         const LanePlan lp = plan_lane(b, cg.g, N, count ? 1 : rows.M, gs, rc, cna, count);
         if (lp.txy) {
@@ -333,9 +312,7 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
     }
     // cells too full for the kernel above (or forced): the round-1 tiled kernel (a slot grid it does not read: the thread-per-atom kernel then)
     if (!done && !count && g_neighbor_variant != 1 && !b.tri && !cg.slot_cap) {
-        int64_t occ = 0;
-        MDH_TRY(occupied_cells_hint(sc, cg, N, &occ));
-        const TiledPlan plan = plan_tiled(b, cg.g, N, rows.M, occ);
+        const TiledPlan plan = plan_tiled(b, cg.g, N, rows.M, gs.v[0]);
         if (plan.tile) {
             MDH_TRY(ensure_unpacked(sc, const_cast<CellGrid &>(cg), N));
             MDH_TRY(launch_neighbor_tiled(sc, cg, plan, N, b, rc, rows, tf));
@@ -350,7 +327,7 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
     return MDH_OK;
 }
 
-// the grid of a build of neighbor rows of `row_width` slots (0: not known, or counting): atoms wrapped, cells in reference order
+// the grid of a build of neighbor rows of `row_width` slots (0: not known, or counting; < 0: GridRequest::row_width): atoms wrapped, cells in reference order
 static GridRequest rows_grid(const int64_t *key, int64_t row_width)
 {
     GridRequest rq;
@@ -561,8 +538,8 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
     MDH_TRY(neighbor_grid_dims(b, rc, cg.g));
     {
         ProfRange pr("cell_grid", st);
-        // (row width: what the last build of this (N, grid) found; 0: none yet)
-        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rows_grid(dkey, width_hint(N, cg.g.ncell, -1)), cg));
+        // (row width: what the last build of this signature found, GridFeedback::width)
+        MDH_TRY(build_cell_grid(sc, dx, dy, dz, N, b, rows_grid(dkey, -1), cg));
     }
     RowsDone pass;
     // Width hint: the largest count the previous call with the same (N, grid) found.  A sequence of calls on one system (a
@@ -570,7 +547,7 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
     // width at once and the counts written by the build confirm it — the counting pass is skipped.  A wrong hint costs one
     // wasted build (the counts are then known) and is replaced; results never depend on it.
     int hmax = 0;
-    const int hint = space == MDH_DEVICE ? width_hint(N, cg.g.ncell, -1) : 0; // (host buffers: a discarded first allocation would still be a copy-back target)
+    const int hint = space == MDH_DEVICE ? cg.fb->width.load(std::memory_order_relaxed) : 0; // (host buffers: a discarded first allocation would still be a copy-back target)
     bool built = false;
     // rows of width M from the caller's allocator, the build, its labels.  confirm: the largest count goes to hmax behind the build
     auto build_rows = [&](int64_t M, bool confirm) {
@@ -605,7 +582,7 @@ int mdh_build_neighbor_exact_fcna(const double *x, const double *y, const double
     }
     const int64_t M = hmax > 1 ? hmax : 1;
     *width = M;
-    width_hint(N, cg.g.ncell, (int)(M <= 4096 ? M : 0));
+    cg.fb->width.store((int)(M <= 4096 ? M : 0), std::memory_order_relaxed);
     if (!built) MDH_TRY(build_rows(M, /*confirm=*/false));
     MDH_HIP(hipGetLastError());
     return sc.finish(space);

@@ -58,8 +58,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 namespace mdh {
 namespace lane {
@@ -1174,57 +1172,39 @@ __global__ __launch_bounds__(256) void k_grid_stats(const int *__restrict__ cell
         if (hist[k]) atomicAdd(&out[k], hist[k]);
 }
 
-namespace {
-struct StatEntry { int64_t N, ncell; int device; int *host; unsigned calls; };
-std::mutex g_stat_mu;
-std::vector<StatEntry> g_stat;
-} // namespace
-
 } // namespace lane
 
-int grid_stats_hint(Scope &sc, const CellGrid &cg, int64_t N, GridStats *out)
+// No lock: the record is the signature's for good (GridFeedback), and two threads that meet a fresh signature together both count
+// and both wait — the same numbers into the same words.
+int grid_stats_hint(Scope &sc, const CellGrid &cg, GridStats *out)
 {
     using namespace lane;
     hipStream_t st = sc.stream();
-    int device = 0;
-    (void)hipGetDevice(&device);
-    std::lock_guard<std::mutex> lk(g_stat_mu);
-    auto count = [&](int *host_dst) -> int {
+    GridFeedback &fb = *cg.fb;
+    auto count = [&]() -> int {
         int *dcnt = sc.alloc_n<int>(GridStats::NBIN);
         if (sc.failed())
             return sc.error();
         MDH_HIP(hipMemsetAsync(dcnt, 0, sizeof(int) * GridStats::NBIN, st));
         const int blocks = (int)std::min<int64_t>((cg.g.ncell / 64 + 255) / 256 + 1, 2048);
         hipLaunchKernelGGL(k_grid_stats, dim3(blocks), dim3(256), 0, st, cg.cell_start, cg.g, dcnt, cg.slot_cap);
-        MDH_HIP(hipMemcpyAsync(host_dst, dcnt, sizeof(int) * GridStats::NBIN, hipMemcpyDeviceToHost, st));
+        MDH_HIP(hipMemcpyAsync(fb.host, dcnt, sizeof(int) * GridStats::NBIN, hipMemcpyDeviceToHost, st));
         return MDH_OK;
     };
-    auto read = [&](const int *host) {
-        // the copy may be landing right now: a torn read mixes two generations of a slowly drifting statistic
-        for (int k = 0; k < GridStats::NBIN; ++k) out->v[k] = ((const volatile int *)host)[k];
-        if (out->v[0] <= 0) out->v[0] = (int)std::min<int64_t>(cg.g.ncell, 2147483647);
-        out->last_listed = ((const volatile int *)host)[GridStats::NBIN];
-        out->listed_sink = const_cast<int *>(host) + GridStats::NBIN;
-    };
-    for (auto &e : g_stat)
-        if (e.N == N && e.ncell == cg.g.ncell && e.device == device) {
-            read(e.host);
-            if ((++e.calls & 7u) == 0) // the occupied region of a running simulation drifts slowly: recount every 8th call
-                MDH_TRY(count(e.host));
-            return MDH_OK;
-        }
-    int *host = nullptr;
-    if (g_stat.size() >= 64) { // keep the table small: the oldest signature hands its pinned block on (never freed: a copy
-        host = g_stat.front().host; // enqueued on some other stream may still land in it — a wrong hint at worst)
-        g_stat.erase(g_stat.begin());
-    } else {
-        MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&host), sizeof(int) * (GridStats::NBIN + 1), hipHostMallocDefault));
+    const bool fresh = fb.calls.load(std::memory_order_relaxed) == 0;
+    if (fresh) { // first sight of the signature: the only build that waits
+        MDH_TRY(count());
+        MDH_HIP(hipStreamSynchronize(st));
+        fb.calls.store(1, std::memory_order_relaxed);
     }
-    host[GridStats::NBIN] = -1; // tiles listed for the second pass: written by the device (k_neighbor_lane, second pass)
-    MDH_TRY(count(host));
-    MDH_HIP(hipStreamSynchronize(st));
-    read(host);
-    g_stat.push_back(StatEntry{N, cg.g.ncell, device, host, 0u});
+    // the copy may be landing right now: a torn read mixes two generations of a slowly drifting statistic
+    const volatile int *host = fb.host;
+    for (int k = 0; k < GridStats::NBIN; ++k) out->v[k] = host[k];
+    if (out->v[0] <= 0) out->v[0] = (int)std::min<int64_t>(cg.g.ncell, 2147483647);
+    out->last_listed = host[GridFeedback::LISTED]; // written by the device (k_neighbor_lane's second pass, or the mop-up)
+    out->listed_sink = fb.host + GridFeedback::LISTED;
+    if (!fresh && (fb.calls.fetch_add(1, std::memory_order_relaxed) & 7u) == 0) // the occupied region of a running simulation drifts slowly: recount every 8th call
+        MDH_TRY(count());
     return MDH_OK;
 }
 
@@ -1525,17 +1505,6 @@ extern "C" int mdh_debug_lane_stamps(unsigned long long *out, int n)
 #endif
 namespace mdh { int lane_last_listed() { return lane::g_last_listed; } }
 namespace mdh { int last_grid_was_slot(); } // cell_grid.hip
-namespace mdh {
-int lane_listed_hint(int64_t N, int64_t ncell)
-{
-    int device = 0;
-    (void)hipGetDevice(&device);
-    std::lock_guard<std::mutex> lk(lane::g_stat_mu);
-    for (auto &e : lane::g_stat)
-        if (e.N == N && e.ncell == ncell && e.device == device) return ((const volatile int *)e.host)[GridStats::NBIN];
-    return -1;
-}
-} // namespace mdh
 extern "C" int mdh_debug_neighbor_plan(int *plan8)
 {
     for (int k = 0; k < 8; ++k) plan8[k] = mdh::lane::g_last_plan[k];

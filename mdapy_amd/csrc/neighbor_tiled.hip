@@ -32,15 +32,13 @@
 // same pass writes the -1 / rc+1 pads.
 //
 // Partly empty boxes (vacuum around a slab or a particle, a rank's slab of a decomposed system).  The tile shape is sized
-// for the population of the OCCUPIED region (occupied_cells_hint: counted on the device, read by the next call), the XCD
+// for the population of the OCCUPIED region (GridStats::v[0]: counted on the device, read by the next call), the XCD
 // chunks are cut from the list of tiles that hold centre atoms (k_tile_live + scan), and the launch grid follows the same
 // estimate — a workgroup takes further tiles of its chunk when the estimate was too small.  A box that is full of atoms
 // takes the straight-line instance (LIST = false): workgroup b owns tile b.
 #include "common.hpp"
 #include "grid.hpp"
 #include <algorithm>
-#include <mutex>
-#include <vector>
 
 namespace mdh {
 
@@ -421,80 +419,11 @@ static TileShape choose_shape(double pop)
     return best;
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// How many cells hold atoms?  The tile shape is sized for the population of the OCCUPIED cells: a box that is mostly empty
-// (vacuum around a slab or a particle, the other ranks' slabs of a decomposed system) would otherwise get tiles whose
-// halo overflows LDS wherever the atoms are.  The count is taken on the device in every call; the host uses the value the
-// previous call with the same (N, grid) left in pinned memory — an MD-style sequence of calls never waits for it — and
-// waits only the first time it sees a new (N, grid).  A stale value costs speed, never correctness (overflowing tiles
-// fall back to the thread-per-atom kernel).
-// counted in blocks of 4 x 4 x 4 cells (a block counts with all its cells as soon as one of them holds an atom): the empty
-// cells that a lattice leaves between its occupied ones belong to the occupied region, vacuum does not
-__global__ __launch_bounds__(256) void k_count_occupied(const int *__restrict__ cell_start, Grid g, int *__restrict__ out)
-{
-    const int nb0 = (g.nc[0] + 3) >> 2, nb1 = (g.nc[1] + 3) >> 2, nb2 = (g.nc[2] + 3) >> 2;
-    const int64_t nblk = (int64_t)nb0 * nb1 * nb2;
-    int mine = 0;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nblk; q += (int64_t)gridDim.x * blockDim.x) {
-        const int b2 = (int)(q % nb2), b1 = (int)((q / nb2) % nb1), b0 = (int)(q / ((int64_t)nb2 * nb1));
-        const int x1 = min(b0 * 4 + 4, g.nc[0]), y1 = min(b1 * 4 + 4, g.nc[1]), z0 = b2 * 4, z1 = min(z0 + 4, g.nc[2]);
-        bool any = false;
-        for (int a = b0 * 4; a < x1 && !any; ++a)
-            for (int c = b1 * 4; c < y1 && !any; ++c) {
-                const int64_t col = ((int64_t)a * g.nc[1] + c) * g.nc[2];
-                any = cell_start[col + z1] > cell_start[col + z0];
-            }
-        if (any) mine += (x1 - b0 * 4) * (y1 - b1 * 4) * (z1 - z0);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(out, mine);
-}
-
-namespace {
-struct OccEntry { int64_t N, ncell; int device; int *host; unsigned calls; };
-std::mutex g_occ_mu;
-std::vector<OccEntry> g_occ;
-} // namespace
-
-int occupied_cells_hint(Scope &sc, const CellGrid &cg, int64_t N, int64_t *occupied)
-{
-    hipStream_t st = sc.stream();
-    int device = 0;
-    (void)hipGetDevice(&device);
-    std::lock_guard<std::mutex> lk(g_occ_mu);
-    auto count = [&](int *host_dst) -> int {
-        int *dcnt = sc.alloc_n<int>(1);
-        if (sc.failed())
-            return sc.error();
-        MDH_HIP(hipMemsetAsync(dcnt, 0, sizeof(int), st));
-        const int blocks = (int)std::min<int64_t>((cg.g.ncell / 64 + 255) / 256 + 1, 4096);
-        hipLaunchKernelGGL(k_count_occupied, dim3(blocks), dim3(256), 0, st, cg.cell_start, cg.g, dcnt);
-        MDH_HIP(hipMemcpyAsync(host_dst, dcnt, sizeof(int), hipMemcpyDeviceToHost, st));
-        return MDH_OK;
-    };
-    for (auto &e : g_occ)
-        if (e.N == N && e.ncell == cg.g.ncell && e.device == device) {
-            const int last = *(volatile int *)e.host;
-            *occupied = last > 0 ? last : cg.g.ncell;
-            if ((++e.calls & 7u) == 0) // the occupied region of a running simulation drifts slowly: recount every 8th call
-                MDH_TRY(count(e.host));
-            return MDH_OK;
-        }
-    int *host = nullptr;
-    if (g_occ.size() >= 64) { // keep the table small: the oldest signature hands its pinned word on (never freed: a copy
-        host = g_occ.front().host; // enqueued on some other stream may still land in it — a wrong hint at worst)
-        g_occ.erase(g_occ.begin());
-    } else {
-        MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&host), sizeof(int), hipHostMallocDefault));
-    }
-    MDH_TRY(count(host));
-    MDH_HIP(hipStreamSynchronize(st));
-    *occupied = *host > 0 ? *host : cg.g.ncell;
-    g_occ.push_back(OccEntry{N, cg.g.ncell, device, host, 0u});
-    return MDH_OK;
-}
-
+// How many cells hold atoms?  The tile shape is sized for the population of the OCCUPIED region: a box that is mostly empty
+// (vacuum around a slab or a particle, the other ranks' slabs of a decomposed system) would otherwise get tiles whose halo
+// overflows LDS wherever the atoms are.  occupied_cells is GridStats::v[0] of the signature (grid_stats_hint, neighbor_lane.hip:
+// counted on the device in blocks of 4 x 4 x 4 cells, read by the next call).  A stale value costs speed, never correctness
+// (overflowing tiles fall back to the thread-per-atom kernel).
 TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells)
 {
     TiledPlan p{0, 0, false, false, 0};

@@ -277,6 +277,43 @@ def test_neighbor_rows_of_65_to_128_slots_take_the_wide_tile_kernel(kind):
     assert np.array_equal(n2, no) and np.array_equal(v2, vo) and np.array_equal(d2, do)
 
 
+@pytest.mark.parametrize("kind", ["full", "half_empty_open_z", "full_forced"])
+def test_neighbor_cells_too_full_for_the_tile_kernel_take_the_round1_tiled_kernel(kind):
+    """Rattled fcc Cu in 13^3 unit cells (8 788 atoms), rc = 6.63 A, rows of 120 slots: 7 grid cells per axis, 25.6 atoms per cell
+    of the occupied region (23.3 with the upper half along z emptied and z open: 196 of the 343 cells are occupied, the tiled kernel
+    walks its list of live tiles).  The tile kernel's planner refuses rows of more than 64 slots beyond 19.5 atoms per cell
+    (mdh_debug_neighbor_plan [6] == -7) and the round-1 tiled kernel takes the call, its tile sized by the same statistics the
+    planner read.  Two builds each — the first of a signature waits for the count, the second reads what the first left — and one
+    under the forced variant; rows, distances and counts bit for bit vs the oracle.
+    (rc: the issue named 6.5 A; there, and at most cutoffs that give 7 cells, 9 ... 17 % of the 3-cell z-runs hold 89 atoms or more —
+    the cells are not commensurate with the lattice planes — and the planner refuses earlier, with -5.  At 6.63 A it is 2.9 % and
+    2.6 %, below that rule's 5 %.)"""
+    from mdapy_amd import _lib
+    pos, box = _fcc(13, 0.05, 7)
+    rc, M = 6.63, 120
+    bnd = PBC
+    if kind == "half_empty_open_z":
+        pos = pos[pos[:, 2] < 0.5 * box[2][2]]
+        bnd = np.array([1, 1, 0], np.int32)
+    assert int(box[0][0] // rc) == 7 and len(pos) / (196 if kind == "half_empty_open_z" else 343) > 19.5
+    x, y, z = _xyz(pos)
+    va = np.full((len(x), M), -1, np.int32); da = np.full((len(x), M), rc + 1.0); na = np.zeros(len(x), np.int32)
+    O.build_neighbor(x, y, z, box, ORG0, bnd, rc, va, da, na, 4)
+    assert 64 < na.max() <= M
+    _lib.lib().mdh_debug_set_neighbor_variant(2 if kind == "full_forced" else 0)
+    try:
+        for call in range(2):
+            vb = np.empty((len(x), M), np.int32); db = np.empty((len(x), M)); nb = np.empty(len(x), np.int32)
+            _neighbor.build_neighbor(x, y, z, box, ORG0, bnd, rc, vb, db, nb, 1, fill_pads=True)
+            if kind != "full_forced":
+                plan = np.zeros(8, np.int32)
+                _lib.lib().mdh_debug_neighbor_plan(plan.ctypes.data)
+                assert plan[0] == 0 and plan[6] == -7, (call, plan.tolist())
+            assert np.array_equal(nb, na) and np.array_equal(vb, va) and np.array_equal(db, da), call
+    finally:
+        _lib.lib().mdh_debug_set_neighbor_variant(0)
+
+
 def test_fused_neighbor_fcna_equals_the_two_calls():
     """mdh_build_neighbor_fcna == mdh_build_neighbor then mdh_fcna, bit for bit (lists AND labels), on every kind of tile the
     kernel meets: interior, periodic seam, open faces, atoms handed in outside the box / unwrapped (the stand-by kernel

@@ -271,3 +271,46 @@ def test_switched_off():
     assert slot  # (the history was kept all along)
     for out, _ in outs:
         _same("off", out, got)
+
+
+def test_record_handed_on_after_64_signatures():
+    """what a signature's builds leave for the next one is kept for 64 signatures (cell_grid.hip grid_feedback): 70 further ones
+    — the same box with the last k = 1 ... 70 atoms dropped — take over the record of the first, whose next build is a first one
+    again: compact, then slot.  Every result equals the compact one, also that of a system whose record went the same way"""
+    pos, box = _lattice(10, 10, 10)
+    _calls("first", pos, box)  # compact, slot, slot
+    for k in range(1, 71):
+        got, _ = _build(pos[:-k], box)
+        _same(("dropped", k), got, _compact(pos[:-k], box))
+    _calls("first, again", pos, box, forms=(False, True))
+    got, _ = _build(pos[:-3], box)
+    _same(("dropped", 3, "again"), got, _compact(pos[:-3], box))
+
+
+def test_forgetting_the_slot_history_forgets_only_that():
+    """mdh_debug_set_slot_grid(2) in the middle of a sequence: the next build is a first one (compact), the one after it a slot
+    build — the tiles listed, which the rule also asks for, were not forgotten.  Nor is the exact row width, which shares the
+    signature's record: the exact-width build (HBM-resident, the calls that use it) returns the oracle's rows.  (Results only: a
+    right width and a forgotten one both make the row allocator run once, so the suite cannot tell them apart.)"""
+    import torch
+    from oracle import oracle as O
+
+    L = _lib.lib()
+    pos, box = _lattice(12, 12, 12, 0.05, seed=22)
+    x, y, z = _xyz(pos)
+    want = O.build_neighbor_without_max_neigh(x, y, z, box, ORG0, PBC, RC, 4)
+    dev = tuple(torch.from_numpy(a).cuda() for a in (x, y, z))
+
+    def exact():
+        got = _neighbor.build_neighbor_without_max_neigh(*dev, box, ORG0, PBC, RC, 1)
+        for name, a, b in zip(("rows", "distances", "counts"), got, want):
+            assert np.asarray(a).shape == b.shape and np.array_equal(np.asarray(a), b), name
+
+    ref = _calls("before", pos, box)  # compact, slot, slot
+    exact()  # (leaves the width)
+    L.mdh_debug_set_slot_grid(L.mdh_debug_set_slot_grid(2))
+    for k, want_slot in enumerate((False, True)):
+        got, slot = _build(pos, box)
+        assert slot == want_slot, ("after", k)
+        _same(("after", k), got, ref)
+    exact()

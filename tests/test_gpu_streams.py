@@ -61,3 +61,41 @@ def test_two_streams_share_the_scratch_cache():
     for t in threads:
         t.join()
     assert not bad, bad
+
+
+def test_two_threads_build_two_signatures():
+    """two host threads, each with its own stream and a system of its own (4 000 and 4 012 atoms), four builds each at the same
+    time: each signature's record (cell_grid.hip grid_feedback) is looked up under one lock that no thread holds while it counts,
+    copies or waits.  Every result equals the compact build's, made beforehand on the main thread"""
+    import torch
+    from test_gpu_slot_grid import M, RC, _compact, _lattice, _same, _spread_and_packed, _xyz
+
+    box = _lattice(10, 10, 10)[1]
+    systems = [_lattice(10, 10, 10)[0], _spread_and_packed()[0]]
+    assert [len(p) for p in systems] == [4000, 4012]
+    want = [_compact(p, box) for p in systems]
+    bad = []
+
+    def worker(k):
+        try:
+            stream = torch.cuda.Stream()
+            with torch.cuda.stream(stream):
+                n = len(systems[k])
+                tx, ty, tz = (torch.from_numpy(a).cuda() for a in _xyz(systems[k]))
+                for it in range(4):
+                    v = torch.empty((n, M), dtype=torch.int32, device="cuda")
+                    d = torch.empty((n, M), dtype=torch.float64, device="cuda")
+                    c = torch.zeros(n, dtype=torch.int32, device="cuda")
+                    p = torch.zeros(n, dtype=torch.int32, device="cuda")
+                    _neighbor.build_neighbor_fcna(tx, ty, tz, box, ORG0, PBC, RC, v, d, c, p, 1, fill_pads=True)
+                    stream.synchronize()
+                    _same((k, it), tuple(t.cpu().numpy() for t in (v, d, c, p)), want[k])
+        except Exception as e:  # (an assertion in a thread would go unseen)
+            bad.append((k, repr(e)))
+
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not bad, bad
