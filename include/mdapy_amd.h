@@ -670,6 +670,37 @@ int mdh_cluster(const int *verlet, const double *dist, const int *nn, int64_t N,
 int mdh_filter_by_type(int *verlet, const double *dist, const int *nn, const int *type, int64_t N, int64_t M,
                        const int *t1_host, const int *t2_host, const double *r_host, int ntype, int space, void *stream);
 
+/* ---- _build_bond ------------------------------------------------------ */
+/* replaces _build_bond.build_bond                           src/build_bond.cpp:10-89, and the np.unique of System.create_bonds
+ * (src/mdapy/system.py:1402-1411).  bond (cap, 2) i32 receives the bonded pairs in lexicographic order: i ascending, j ascending
+ * inside a row.  A pair (i, j) is listed when j sits in slots 0 .. nn[i] - 1 of row i, j > i, both types lie in 0 .. ntype - 1
+ * (otherwise the pair is skipped, build_bond.cpp:50) and dist <= cutoff[ti * ntype + tj] (a tie is a bond); an entry outside
+ * 0 .. N - 1 is no bond, a key that a row holds twice is listed once.  type (N) i32, compact, or NULL: every atom is type 0.
+ * cutoff_host (ntype, ntype) f64, row-major, host memory, every entry positive and finite.
+ * n_real == 0: plain.  n_real > 0: the list was built on a replica of n_real atoms (copy c of atom a is entry c * n_real + a):
+ * only rows 0 .. n_real - 1 are read, a slot's key is j % n_real and it is the key that must exceed i, a slot's type is that of
+ * replica atom j; two images of one atom in a row are one bond.
+ * *count_host (host memory) = the number of bonds.  bond == NULL: the count alone.  More bonds than cap: MDH_ERR_ARG, the count
+ * still delivered.  ntype < 1, a cutoff that is not a positive number, n_real > N, M > 4096 or rows * M > 2^31 - 1 (the bonds a list
+ * could hold, which int32 must index): MDH_ERR_ARG before any device work.  N may be 0.  Slots come from prefix sums in row order
+ * and a rank inside the row: the same input gives the same bits.  Waits for the stream (the count is read back). */
+int mdh_build_bond(const int *verlet, const double *dist, const int *nn, int64_t N, int64_t M,
+                   const int *type /* (N) compact 0..ntype-1, or NULL = all 0 */,
+                   const double *cutoff_host /* ntype*ntype, row-major */, int ntype,
+                   int64_t n_real /* 0: plain; >0: rows 0..n_real-1 only, keys j % n_real */,
+                   int *bond /* (cap, 2) or NULL */, int64_t cap, int64_t *count_host, int space, void *stream);
+/* comp (n_cluster, ntype) i32, cleared here: comp[cluster_id[a] - 1][type[a]] += 1 for every atom a (System.cal_chemical_species,
+ * src/mdapy/system.py:2680-2690: what a molecule is made of).  An id outside 1 .. n_cluster or a type outside 0 .. ntype - 1:
+ * MDH_ERR_ARG (found on the device; comp is then not to be used).  Integer sums: the same bits on every run.  Waits for the stream. */
+int mdh_cluster_composition(const int *cluster_id, const int *type, int64_t N, int n_cluster, int ntype, int *comp, int space,
+                            void *stream);
+/* want_host (nspecies, ntype) i32 and counts_host (nspecies) i64 in host memory: counts_host[s] = the rows of comp that equal
+ * want_host[s].  mol_id (N) i32 or NULL: mol_id[a] = the species that row cluster_id[a] - 1 equals, -1 for none (and for an id
+ * outside 1 .. n_cluster).  Where two species have the same composition both get the full count and mol_id the LAST index (the
+ * reference's {name: index} dict, system.py:2705).  Waits for the stream. */
+int mdh_species_match(const int *comp, int n_cluster, int ntype, const int *want_host, int nspecies, const int *cluster_id, int64_t N,
+                      int *mol_id, int64_t *counts_host, int space, void *stream);
+
 /* replaces _fccpft.identify_sftb_fcc                       src/identify_fcc_planar_faults.cpp:54-245
  * hcp_indices (n_hcp) ascending atom ids with structure type 2; hcp_neighbors (n_hcp,12) caller scratch (written);
  * ptm_indices (N,12) = columns 1..12 of the PTM neighbour rows; fault_types (N) pre-zeroed, HCP entries written:

@@ -23,6 +23,7 @@ from .mean_squared_displacement import MeanSquaredDisplacement
 from .void_analysis import VoidAnalysis
 from .trajectory import Trajectory
 from .unwrap_trajectory import unwrap_trajectory
+from .vdw_radii import VDW_RADII, vdw_radius
 from .build_lattice import build_crystal
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
@@ -31,6 +32,6 @@ __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
     "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
-    "Trajectory", "unwrap_trajectory",
+    "Trajectory", "unwrap_trajectory", "VDW_RADII", "vdw_radius",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

@@ -119,6 +119,9 @@ _SIGNATURES = {
     "mdh_fill_cell_for_void": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, i64, cint, vp],
     "mdh_void_points": [vp, cint, cint, cint, vp, vp, vp, vp, vp, vp, i64, vp, cint, vp],
     "mdh_void_prune": [vp, vp, vp, vp, i64, cint, vp, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_build_bond": [vp, vp, vp, i64, i64, vp, vp, cint, i64, vp, i64, vp, cint, vp],
+    "mdh_cluster_composition": [vp, vp, i64, cint, cint, vp, cint, vp],
+    "mdh_species_match": [vp, cint, cint, vp, cint, vp, i64, vp, vp, cint, vp],
     "mdh_repeat_cell": [vp, vp, vp, i64, cint, cint, cint, cint, vp],
     "mdh_ptm": [C.c_char_p, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, dbl, vp, cint, vp, cint, cint, vp],
     "mdh_ptm_flags": [C.c_char_p],

@@ -401,6 +401,7 @@ void warm_lindemann(hipStream_t st);
 void warm_msd(hipStream_t st);
 void warm_unwrap(hipStream_t st);
 void warm_voids(hipStream_t st);
+void warm_bonds(hipStream_t st);
 void warm_repeat(hipStream_t st);
 void warm_ptm(hipStream_t st);
 void warm_ptm_stages(hipStream_t st);
@@ -529,6 +530,7 @@ int mdh_warm(void)
     mdh::warm_msd(nullptr);
     mdh::warm_unwrap(nullptr);
     mdh::warm_voids(nullptr);
+    mdh::warm_bonds(nullptr);
     mdh::warm_repeat(nullptr);
     mdh::warm_ptm(nullptr);
     mdh::warm_ptm_stages(nullptr);

@@ -10,6 +10,9 @@ from . import _atomtemp as atomtemp
 # its tests install a restatement of their own as kernels.bond_analysis — one by one, or all of them with
 # tests/_oracle_backend.py's install_consumers, as the randomised sweeps do)
 from . import _bond_analysis as bond_analysis
+# (not in NAMES either: the oracle has no adapter for the bond pairs and the molecule compositions; their tests install a
+# restatement as kernels.build_bond)
+from . import _build_bond as build_bond
 # (not in NAMES either: the oracle has no CHILL+; its tests install a restatement as kernels.chill_plus)
 from . import _chill_plus as chill_plus
 from . import _cluster as cluster
