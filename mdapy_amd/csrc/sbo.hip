@@ -22,11 +22,25 @@ static constexpr double MY_PI = 3.14159265358979323846;
 
 struct LList { int l[SBO_MAXL]; int n; };
 
-__device__ __forceinline__ double assoc_legendre(int l, int m, double x) // :243-268
+// sin(theta) of a bond (dx, dy, dz) whose listed length is r, x = dz / r.  The reference takes sqrt(1 - x * x), which cancels near the
+// poles: a bond 1e-3 rad off the z axis put 1e-13 into q_lm, a bond exactly on the axis put 1e-8 there when its cosine rounded to
+// 1 - 2^-53 and NaN when it rounded to 1 + 2^-52 (a perfect hexagonal lattice does that).  rxy / r does not, and is the same number
+// in exact arithmetic as long as r is the length of (dx, dy, dz).  Where it is not — a list whose entry belongs to another periodic
+// image than the minimum image formed here, in a box thinner than two bond lengths — the reference's expression stays, and with it
+// what the reference computes there.  (Found by tests/test_gpu_steinhardt.py against exact harmonics; the oracle computes the same.)
+__device__ __forceinline__ double bond_sine(double x, double rxy2, double dz, double r)
+{
+    const double r2 = r * r;
+    if (fabs(rxy2 + dz * dz - r2) <= 1e-12 * r2)
+        return sqrt(rxy2) / r;
+    return sqrt(1.0 - x * x);
+}
+
+// :243-268, with sin(theta) handed in (bond_sine)
+__device__ __forceinline__ double assoc_legendre(int l, int m, double x, double sqx)
 {
     double p = 1.0, pm1 = 0.0, pm2 = 0.0;
     if (m != 0) {
-        const double sqx = sqrt(1.0 - x * x);
         for (int i = 1; i < m + 1; ++i)
             p *= (2 * i - 1) * sqx;
     }
@@ -85,14 +99,15 @@ __global__ void k_sq_stage1(const double *__restrict__ x, const double *__restri
         const double rxy2 = er * er + ei * ei;
         if (rxy2 < EPS * EPS) { er = 1.0; ei = 0.0; }
         else { const double s = 1.0 / sqrt(rxy2); er *= s; ei *= s; }
+        const double sqx = bond_sine(ct, rxy2, dz, r);
         for (int il = 0; il < nl; ++il) {
             const int l = ll.l[il];
             const int o = il * nz;
             const double *nrm = norm + il * (lmax + 1);
-            QR(o + l) += w * (nrm[0] * assoc_legendre(l, 0, ct));
+            QR(o + l) += w * (nrm[0] * assoc_legendre(l, 0, ct, sqx));
             double mr = er, mi = ei;
             for (int m = 1; m < l + 1; ++m) {
-                const double pf = nrm[m] * assoc_legendre(l, m, ct);
+                const double pf = nrm[m] * assoc_legendre(l, m, ct, sqx);
                 const double cr = pf * mr, ci = pf * mi;
                 const double wr = w * cr, wi = w * ci;
                 QR(o + l + m) += wr;
@@ -123,7 +138,7 @@ __global__ void k_sq_stage1(const double *__restrict__ x, const double *__restri
 }
 
 // Stage 1 for ONE degree l known at compile time: the 2l+1 running sums of an atom in registers, the Legendre recurrences
-// unrolled (same expressions as assoc_legendre, so the same values; the square root under them is computed once per bond),
+// unrolled (same expressions as assoc_legendre, so the same values),
 // the row segments of the 64 atoms of a workgroup copied in and out through LDS with coalesced accesses.  One launch per
 // entry of llist; sums and their order are those of the generic kernel (bond by bond in list order), bit for bit.
 template <bool TRI, int L>
@@ -213,11 +228,12 @@ __global__ __launch_bounds__(64) void k_sq_stage1_l(const double *__restrict__ x
             const double rxy2 = er * er + ei * ei;
             if (rxy2 < EPS * EPS) { er = 1.0; ei = 0.0; }
             else { const double sc = 1.0 / sqrt(rxy2); er *= sc; ei *= sc; }
-            ar[L] += w * (nrm[0] * assoc_legendre(L, 0, ct));
+            const double sqx = bond_sine(ct, rxy2, dz, r);
+            ar[L] += w * (nrm[0] * assoc_legendre(L, 0, ct, sqx));
             double mr = er, mi = ei;
 #pragma unroll
             for (int m = 1; m < L + 1; ++m) {
-                const double pf = nrm[m] * assoc_legendre(L, m, ct);
+                const double pf = nrm[m] * assoc_legendre(L, m, ct, sqx);
                 const double cr = pf * mr, ci = pf * mi;
                 const double wr = w * cr, wi = w * ci;
                 ar[L + m] += wr;
@@ -358,7 +374,7 @@ __global__ __launch_bounds__(64) void k_sq_stage1_pair(const double *__restrict_
             const double rxy2 = er * er + ei * ei;
             if (rxy2 < EPS * EPS) { er = 1.0; ei = 0.0; }
             else { const double sc = 1.0 / sqrt(rxy2); er *= sc; ei *= sc; }
-            const double sqx = sqrt(1.0 - ct * ct); // (assoc_legendre computes it for every m != 0: the same value)
+            const double sqx = bond_sine(ct, rxy2, dz, r); // as the other stage-1 kernels hand it to assoc_legendre
             double pa, pb;
             legendre_pair<LA, LB>(0, ct, sqx, pa, pb);
             ar[LA] += w * (na[0] * pa);

@@ -612,13 +612,13 @@ static void fact_init(void) /* :12-181 h_factorial: n! as doubles */
     fact_ready = 1;
 }
 
-static double assoc_legendre(int l, int m, double x) /* :243-268 */
+/* :243-268, but sin(theta) is handed in (bond_sine below) */
+static double assoc_legendre(int l, int m, double x, double sqx)
 {
     if (l < m)
         return 0.0;
     double p = 1.0, pm1 = 0.0, pm2 = 0.0;
     if (m != 0) {
-        double sqx = sqrt(1.0 - x * x);
         for (int i = 1; i < m + 1; ++i)
             p *= (2 * i - 1) * sqx;
     }
@@ -630,14 +630,27 @@ static double assoc_legendre(int l, int m, double x) /* :243-268 */
     return p;
 }
 
-static double polar_prefactor(int l, int m, double ct) /* :270-286 */
+/* sin(theta) of a bond (dx, dy, dz) whose listed length is r, x = dz / r.  The reference takes sqrt(1 - x * x), which cancels near
+ * the poles: a bond 1e-3 rad off the z axis puts 1e-13 into q_lm, one exactly on the axis puts 1e-8 there when its cosine rounds
+ * to 1 - 2^-53 and NaN when it rounds to 1 + 2^-52 (a perfect hexagonal lattice does that).  rxy / r does not, and is the same
+ * number in exact arithmetic as long as r is the length of (dx, dy, dz).  Where it is not — a list whose entry belongs to another
+ * periodic image than the minimum image formed here, in a box thinner than two bond lengths — the reference's expression stays. */
+static double bond_sine(double x, double rxy2, double dz, double r)
+{
+    const double r2 = r * r;
+    if (fabs(rxy2 + dz * dz - r2) <= 1e-12 * r2)
+        return sqrt(rxy2) / r;
+    return sqrt(1.0 - x * x);
+}
+
+static double polar_prefactor(int l, int m, double ct, double st) /* :270-286 */
 {
     const double PI = 3.14159265358979323846;
     int ma = m < 0 ? -m : m;
     double pf = 1.0;
     for (int i = l - ma + 1; i < l + ma + 1; ++i)
         pf *= i;
-    pf = sqrt((2 * l + 1) / (4 * PI * pf)) * assoc_legendre(l, ma, ct);
+    pf = sqrt((2 * l + 1) / (4 * PI * pf)) * assoc_legendre(l, ma, ct, st);
     if ((m < 0) && (m % 2))
         pf = -pf;
     return pf;
@@ -733,13 +746,14 @@ ORC_API int orc_get_sq(const double *x, const double *y, const double *z, int64_
             double rxy2 = er * er + ei * ei;
             if (rxy2 < EPS * EPS) { er = 1.0; ei = 0.0; }
             else { double s = 1.0 / sqrt(rxy2); er *= s; ei *= s; }
+            double st = bond_sine(ct, rxy2, dz, r);
             for (int il = 0; il < nl; ++il) {
                 int l = llist[il];
                 double *pr = qr + il * nz, *pi = qi + il * nz;
-                pr[l] += w * polar_prefactor(l, 0, ct);
+                pr[l] += w * polar_prefactor(l, 0, ct, st);
                 double mr = er, mi = ei;
                 for (int m = 1; m < l + 1; ++m) {
-                    double pf = polar_prefactor(l, m, ct);
+                    double pf = polar_prefactor(l, m, ct, st);
                     double cr = pf * mr, ci = pf * mi;
                     double wr = w * cr, wi = w * ci;
                     pr[l + m] += wr;

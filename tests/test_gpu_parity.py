@@ -3,7 +3,8 @@ libmdapy_amd.so), against (1) the CPU oracle on the same seeded inputs, (2) the 
 reference's test-suite, (3) size-independent properties at large N.
 
 Bars: bit-exact for integer outputs (neighbor ids, counts, labels, histogram counts) and — where the
-arithmetic is IEEE-exact — for distances; 1e-6 relative for floating-point outputs (CSP, q_l, g(r)).
+arithmetic is IEEE-exact — for distances; 1e-6 relative for floating-point outputs (CSP, q_l, g(r)).  The Steinhardt columns
+(q_lm, q_l, w_l, w_l-hat) have a far tighter bar of their own, against exact mathematics: tests/test_gpu_steinhardt.py.
 """
 import json
 import os
