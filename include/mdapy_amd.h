@@ -104,6 +104,43 @@ int mdh_debug_set_indirect(int on);
 int mdh_debug_set_slot_grid(int on);
 int mdh_debug_slot_grid_counters(int64_t *out4);
 int mdh_debug_slot_grid_rule(int ordered, int keyed, int windowed, int row_width, int64_t ncell, int64_t N, int seen, int big, int listed);
+/* test hook: what a cell grid build decides before it enqueues anything (csrc/grid_plan.hpp plan_grid), on the host: no device is touched.
+ * in24:
+ *   [0]  what the atoms are wanted as: 0 sorted coordinate arrays, 1 for neighbor rows, 2 for rows of input known to be unordered
+ *   [1]  1: every cell's atoms in descending order
+ *   [2]  1: by a sort key instead of the id
+ *   [3]  1: the slot grid may be taken (a build behind the neighbor pass)
+ *   [4]  width of the rows about to be built (0: not known; < 0: the signature's last exact width, [20])
+ *   [5]  atoms
+ *   [6]  cells
+ *   [7], [8], [9]  cells per axis
+ *   [10] grid mode (0: rc-wide cells)
+ *   [11] 1: a triclinic box
+ *   [12] 1: a cell window is pending (mdh_hint_cell_window), [13] its axis
+ *   [14] 1: a centre window is pending (mdh_hint_centre_window), [15] its axis
+ *   [16] the order hint's word (1: the last sample found the atoms in no spatial order)
+ *   [17] 1: the hint asks this build to sample the order again
+ *   [18] the signature's history: -1 no build has finished, 0 the last one saw no cell of more than eight atoms, 1 it saw one
+ *   [19] tiles the last build listed (-1: not known)
+ *   [20] the signature's last exact row width
+ *   [21] the switch of mdh_debug_set_indirect, [22] of mdh_debug_set_slot_grid, [23] MDH_SLOT_GRID_FORCE
+ * in6:
+ *   [0]  1 / rc
+ *   [1]  box length along axis 0
+ *   [2], [3]  the cell window's fractions lo, hi
+ *   [4], [5]  the centre window's fractions lo, hi
+ * out15:
+ *   [0]  form: 0 sorted arrays, 1 records gathered, 2 records moved whole, 3 indirect, 4 slot grid
+ *   [1]  1: the build keeps the signature's history
+ *   [2]  1: it samples the order of the atoms
+ *   [3]  1: four atoms per lane while binning
+ *   [4], [5]  planes [p0, p1) of axis 0 that hold atoms, [6], [7] and [p2, p3)
+ *   [8]  1: the passes over the grid run over those planes only
+ *   [9], [10]  planes of a one-piece window the tile kernel runs over (0, 0: all)
+ *   [11], [12] planes whose atoms want rows (0, 0: all)
+ *   [13] in-cell sort: 0 none, 1 dense cells, 2 a thread per cell, 3 per piece of the window
+ *   [14] the row width resolved */
+int mdh_debug_grid_plan(const int64_t *in24, const double *in6, int *out15);
 /* test hook: the tile plan of the last neighbor build that took the LDS-tile kernel (neighbor_lane.hip):
  * plan8 = {tile cells in x/y, in z, halo atoms per tile, LDS bytes, box full of atoms, 1000 * atoms per cell,
  * cells of the occupied region, 1 if a plan was made since the last query}; bit 8 of plan8[4]: the build's cell grid was a slot grid. */

@@ -14,9 +14,14 @@
 //   count u32[ncell] (two arrays in one kept block, alternating from one slot build to the next), slots i32[2][ncell][4] (the ids
 //   of a cell where its counter placed them, then sorted in place: k_assign<SLOT> -> k_sort_slots, no scan, no scatter),
 //   spill int2[N] + a counter (the atoms of cells that hold more than SLOT_CAP).
+// A build (build_cell_grid, at the end of the namespace): the thread's window hints are taken, the signature's feedback record is
+// looked up and its pinned words read, plan_grid (grid_plan.hpp: pure, tested on the host) decides the form, the window's planes and
+// the in-cell sort from those values, the buffers of that form are allocated, and file-static steps that only enqueue carry the plan
+// out: bin_atoms, then finish_slot_grid, or scan_cells, k_scatter, sort_cells, gather_atoms.
 #include "common.hpp"
 #include "grid.hpp"
 #include "assign_groups.hpp"
+#include "grid_plan.hpp"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -637,7 +642,6 @@ int ensure_unpacked(Scope &sc, CellGrid &cg, int64_t N)
 // served as before.  An atom binned outside the promised window breaks the promise: counted on the device, reported by
 // the next call of this thread that builds a grid.
 // ----------------------------------------------------------------------------
-struct CellWindow { int axis = 0; double lo = 0.0, hi = 0.0; bool set = false; };
 // The hints for the NEXT grid build of this thread: the window, and inside it the stretch that holds the atoms whose rows are wanted
 // (mdh_hint_centre_window: a rank's OWN slab; what lies between it and the window's ends are ghosts — candidates of the tile
 // kernel, never its centres: their rows are not made)
@@ -768,8 +772,8 @@ static std::atomic<int> g_slot_grid{[] { const char *e = std::getenv("MDH_SLOT_G
 // MDH_SLOT_GRID_FORCE=1 (a measuring switch, profiles/slot_grid.md): the slot grid wherever its layout allows, whatever the history
 // says — what a build that meets full cells costs (spill list, listed tiles, the thread-per-atom mop-up); results are the same
 static const bool g_slot_force = [] { const char *e = std::getenv("MDH_SLOT_GRID_FORCE"); return e && std::atoi(e) != 0; }();
-static std::atomic<int> g_last_slot_build{0}; // the last FOR_ROWS build of the process was a slot build (mdh_debug_neighbor_plan)
-int last_grid_was_slot() { return g_last_slot_build.load(std::memory_order_relaxed); }
+static std::atomic<int> g_last_form{GridPlan::ARRAYS}; // the form the last grid build of the process was planned in (mdh_debug_neighbor_plan)
+int last_grid_was_slot() { return g_last_form.load(std::memory_order_relaxed) == GridPlan::SLOT; }
 static std::mutex g_slot_mu; // the two tables below: their lookups and hand-overs only, never across a launch, a copy or a wait
 // per KEEP_SLOT block: the half the next slot build counts into (all zero) and the words of each half that are not zero
 struct SlotBlock { void *p; int next; int64_t dirty[2]; };
@@ -819,257 +823,288 @@ static SlotBlock *slot_block_state(void *p)
     return g_slot_blocks.back();
 }
 
-bool slot_grid_rule(bool ordered, bool keyed, bool windowed, int row_width, int64_t ncell, int64_t N, bool seen, bool big, int listed)
+// ----------------------------------------------------------------------------
+// The build: take the hints, look up the record, read the words, plan (grid_plan.hpp), allocate for the plan's form, enqueue.
+// The steps below only enqueue; what they share is one GridBuild.
+// ----------------------------------------------------------------------------
+static_assert((int)GridRequest::SORTED_ARRAYS == GridPlanIn::SORTED_ARRAYS && (int)GridRequest::FOR_ROWS == GridPlanIn::FOR_ROWS &&
+              (int)GridRequest::FOR_ROWS_UNORDERED == GridPlanIn::FOR_ROWS_UNORDERED, "GridPlanIn::Atoms mirrors GridRequest::Atoms");
+
+struct GridBuild {
+    hipStream_t st;
+    const double *x, *y, *z;
+    int64_t N;
+    const DBox &b;
+    const GridRequest &rq;
+    GridPlan pl;
+    unsigned gen = 0; // stamps of this build's k_assign; the (first) scan is launched with the same value
+    // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
+    // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
+    unsigned *cell_count = nullptr, *ctl = nullptr;
+    int2 *ent = nullptr;          // (cell, slot) of every atom: k_assign -> k_scatter; afterwards the N ints of scratch of the in-cell sorts; a slot build: its spill list
+    unsigned short *mv = nullptr; // image codes in input order
+    CellGrid::Packed *rec = nullptr; // records in input order (GridPlan::RECORDS_MOVED)
+    int *hist = nullptr;          // != nullptr: this build keeps the history (the record's two words from BIG on)
+    int *bad = nullptr;           // != nullptr: a windowed build's pinned word for atoms outside the promise
+    // a slot build: the half of a KEEP_SLOT block that the previous slot build's sort cleared, 64 words of header — [0] the length
+    // of the spill list — and the counters behind them (cell_count); the other half, which this build's sort clears
+    unsigned *slot_block = nullptr, *slot_idle = nullptr;
+    int64_t slot_idle_n = 0;
+    SlotBlock *sb = nullptr;
+    bool slot() const { return pl.form == GridPlan::SLOT; }
+};
+
+// the values plan_grid decides by: the request, the grid, the hints, and the words read from the signature's record (cg.fb, looked
+// up here: the passes over the grid reach it through cg.fb) and from the order hint (*order_word: where a sample would go)
+static int read_plan_inputs(const GridRequest &rq, int64_t N, const DBox &b, const double *x, const PendingWindows &hints, CellGrid &cg,
+                            GridPlanIn &in, int **order_word)
 {
-    if (!ordered || keyed || windowed || row_width > 16) return false;
-    if (ncell > 2 * N || ncell * SLOT_CAP >= (int64_t(1) << 31)) return false; // (the slots are indexed with 32 bits; 32 bytes a cell)
-    return seen && !big && listed == 0;
+    const Grid &g = cg.g;
+    in.atoms = (int)rq.atoms; in.sort_desc = rq.sort_desc; in.keyed = rq.sort_key != nullptr; in.slots_ok = rq.slots_ok; in.row_width = rq.row_width;
+    in.N = N; in.ncell = g.ncell; in.mode = g.mode; in.rc_inv = g.rc_inv; in.tri = b.tri; in.h0 = b.h[0];
+    for (int d = 0; d < 3; ++d) in.nc[d] = g.nc[d];
+    in.cells = hints.cells; in.centre = hints.centre;
+    in.indirect_on = g_indirect.load(std::memory_order_relaxed) != 0;
+    in.slot_on = g_slot_grid.load(std::memory_order_relaxed) != 0;
+    in.slot_force = g_slot_force;
+    if (in.has_record()) {
+        MDH_TRY(grid_feedback(N, g.ncell, &cg.fb));
+        const volatile int *host = cg.fb->host;
+        in.big = host[GridFeedback::BIG]; in.listed = host[GridFeedback::LISTED];
+        in.record_width = cg.fb->width.load(std::memory_order_relaxed);
+    }
+    if (in.asks_order()) {
+        const OrderHint h = order_hint(1, N, g.ncell, x);
+        if (h.word) { in.order_word = *(volatile int *)h.word; in.order_sample = h.sample; *order_word = h.word; }
+    }
+    return MDH_OK;
+}
+
+static int allocate_grid(Scope &sc, GridBuild &bd, CellGrid &cg)
+{
+    const Grid &g = cg.g;
+    const size_t N = (size_t)bd.N;
+    if (bd.slot()) {
+        // (+ 64 words behind the counts: the tile kernel reads a cell's count with the word behind it)
+        bd.slot_block = static_cast<unsigned *>(sc.alloc_kept(2 * sizeof(unsigned) * (size_t)(g.ncell + 128), Scope::KEEP_SLOT));
+        if (bd.slot_block) {
+            const size_t half = sc.held_bytes(bd.slot_block) / 8; // words of a half (a block is a multiple of 256 bytes)
+            bd.sb = slot_block_state(bd.slot_block);
+            bd.cell_count = bd.slot_block + (size_t)bd.sb->next * half + 64;
+            bd.slot_idle = bd.slot_block + (size_t)(1 - bd.sb->next) * half;
+            bd.slot_idle_n = std::min<int64_t>(bd.sb->dirty[1 - bd.sb->next], (int64_t)half); // (a freed block's address may come back as a smaller, zero-filled one)
+        }
+        cg.slot_hi = 4 * g.ncell; // where the second plane of four slots per cell starts
+    } else {
+        bd.cell_count = static_cast<unsigned *>(sc.alloc_kept(sizeof(unsigned) * (size_t)g.ncell, Scope::KEEP_ZERO));
+    }
+    bd.ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
+    cg.flags = sc.alloc_n<int>(8);
+    // a slot grid has no entries, no prefix array and counters of its own
+    cg.cell_start = bd.slot() ? reinterpret_cast<int *>(bd.cell_count) : sc.alloc_n<int>((size_t)g.ncell + 1);
+    bd.ent = sc.alloc_n<int2>(N);
+    // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
+    cg.order = sc.alloc_n<int>(bd.slot() ? (size_t)g.ncell * SLOT_CAP + 4 : N + 4);
+    bd.mv = sc.alloc_n<unsigned short>(N);
+    switch (bd.pl.form) {
+    case GridPlan::ARRAYS:
+        cg.xs = sc.alloc_n<double>(N);
+        cg.ys = sc.alloc_n<double>(N);
+        cg.zs = sc.alloc_n<double>(N);
+        cg.mvs = sc.alloc_n<unsigned short>(N);
+        break;
+    case GridPlan::RECORDS_GATHERED: cg.pk = sc.alloc_n<CellGrid::Packed>(N); break;
+    case GridPlan::RECORDS_MOVED: cg.pk = sc.alloc_n<CellGrid::Packed>(N); bd.rec = sc.alloc_n<CellGrid::Packed>(N); break;
+    case GridPlan::INDIRECT: case GridPlan::SLOT: break; // no sorted copy
+    }
+    return sc.failed() ? sc.error() : MDH_OK;
+}
+
+// the order question (k_order_far_flag), asked again: the answer lands in the hint's pinned word for the NEXT builds
+static void sample_order(const GridBuild &bd, int *word)
+{
+    const double *h = bd.b.h;
+    const double vol = std::fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]));
+    const double edge = std::cbrt(64.0 * vol / (double)bd.N);
+    double nb[3];
+    for (int d = 0; d < 3; ++d) nb[d] = std::max(1.0, std::floor(bd.b.thick[d] / edge));
+    hipLaunchKernelGGL(k_order_far_flag, dim3(1), dim3(1024), 0, bd.st, bd.x, bd.y, bd.z, bd.N, bd.b, nb[0], nb[1], nb[2], word);
+}
+
+// binning: every atom takes a slot from its cell's counter — an entry (cell, slot) for the scan and the scatter, or, a slot grid,
+// its id straight into the cell's slots (cg.order) and the spill list (ent; its length in the header word in front of the counts)
+template <bool TRI, int K, bool SLOT>
+static void launch_assign(const GridBuild &bd, const CellGrid &cg)
+{
+    const Grid &g = cg.g;
+    // slack for the raw-vs-wrapped consistency flag: far above rounding, far below a cell width
+    const double slack = 0.01 / (g.rc_inv > 0 ? g.rc_inv : 1.0);
+    // the promise is checked where the atoms are binned (a word of pinned host memory the kernel writes) and read by the next
+    // build of this thread or by mdh_cell_window_check
+    const CellPlanes win{bd.pl.p0, bd.pl.p1, bd.pl.p2, bd.pl.p3, bd.bad};
+    int2 *const ent = SLOT ? nullptr : bd.ent, *const spill = SLOT ? bd.ent : nullptr;
+    int *const slots = SLOT ? cg.order : nullptr;
+    unsigned *const spill_n = SLOT ? bd.cell_count - 64 : nullptr;
+    hipLaunchKernelGGL((k_assign<TRI, K, SLOT>), dim3(grid_for(bd.N, 256 * K)), dim3(256), 0, bd.st, bd.x, bd.y, bd.z, bd.N, bd.b, g, (int)bd.rq.wrap_first,
+                       ent, bd.cell_count, bd.ctl, bd.gen, slack, bd.mv, win, bd.rec, bd.pl.form != GridPlan::ARRAYS ? 1 : 0, slots, spill, spill_n,
+                       SLOT ? cg.slot_hi : (int64_t)0);
+}
+static void bin_atoms(const GridBuild &bd, const CellGrid &cg)
+{
+    switch ((bd.b.tri ? 4 : 0) | (bd.pl.assign4 ? 2 : 0) | (bd.slot() ? 1 : 0)) {
+    case 0: launch_assign<false, 1, false>(bd, cg); break;
+    case 1: launch_assign<false, 1, true>(bd, cg); break;
+    case 2: launch_assign<false, 4, false>(bd, cg); break;
+    case 3: launch_assign<false, 4, true>(bd, cg); break;
+    case 4: launch_assign<true, 1, false>(bd, cg); break;
+    case 5: launch_assign<true, 1, true>(bd, cg); break;
+    case 6: launch_assign<true, 4, false>(bd, cg); break;
+    case 7: launch_assign<true, 4, true>(bd, cg); break;
+    }
+}
+
+// a slot grid: sort in place, done — no scan, no scatter, no gather (the atoms stay where the caller has them, CellGrid::ix)
+static int finish_slot_grid(Scope &sc, const GridBuild &bd, CellGrid &cg)
+{
+    const Grid &g = cg.g;
+    hipLaunchKernelGGL(k_sort_slots, dim3(grid_for(std::max<int64_t>(g.ncell, bd.slot_idle_n), 256)), dim3(256), 0, bd.st, bd.cell_count, cg.order, g.ncell,
+                       bd.slot_idle, bd.slot_idle_n, bd.ctl, bd.gen, bd.hist, cg.flags, cg.slot_hi);
+    MDH_HIP(hipGetLastError());
+    {
+        std::lock_guard<std::mutex> lk(g_slot_mu);
+        SlotBlock *sb = bd.sb;
+        sb->dirty[1 - sb->next] = 0;          // cleared by the sort above
+        sb->dirty[sb->next] = g.ncell + 64;   // this build's header and counts: read until the next slot build's sort clears them
+        sb->next = 1 - sb->next;
+    }
+    sc.keep_confirm(bd.slot_block);
+    cg.big_stamp = bd.ctl + 3; cg.big_gen = bd.gen; cg.big_sink = bd.hist;
+    cg.slot_cap = SLOT_CAP;
+    cg.spill = bd.ent;
+    cg.n_spill = bd.cell_count - 64;
+    cg.ix = bd.x; cg.iy = bd.y; cg.iz = bd.z; cg.imv = bd.mv;
+    return MDH_OK;
+}
+
+// the scan of the bin counters into cg.cell_start: the whole grid, or a window's pieces with cell_start elsewhere filled with what
+// a full scan leaves there
+static int scan_cells(const GridBuild &bd, CellGrid &cg)
+{
+    const Grid &g = cg.g;
+    const GridPlan &pl = bd.pl;
+    hipStream_t st = bd.st;
+    auto scan_piece = [&](int64_t from, int64_t to, unsigned use_gen, int *flags) {
+        launch_scan_gen(st, bd.cell_count + from, cg.cell_start + from, to - from, bd.ctl, use_gen, true, flags); // [to] = the piece's total
+    };
+    if (!pl.windowed) {
+        scan_piece(0, g.ncell, bd.gen, cg.flags);
+        return MDH_OK;
+    }
+    // the pieces in index order: [p0, p1) then [p2, p3); a piece is scanned on its own, the atoms before it added by the
+    // fill / by a second add pass; cell_start elsewhere = what a full scan leaves: the atoms binned so far.  The counters
+    // outside the window are zero (kept block; atoms out there take no slot) and stay untouched.
+    const int64_t plane = (int64_t)g.nc[1] * g.nc[2];
+    const int64_t a0 = pl.p0 * plane, a1 = pl.p1 * plane, b0 = pl.p2 * plane, b1 = pl.p3 * plane;
+    // (a constant fill through the runtime's fill kernel.  Looks unreachable: a window of two pieces starts at plane 0; kept as it stood)
+    if (b1 > b0 && a0 > 0) MDH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cg.cell_start), 0, (size_t)a0, st));
+    // (from a multiple of four cells on: the scan moves 16 bytes per access only from an aligned start — 66 against 26 us for the
+    // 3.6 M cells of a 10 M-atom slab; the up to three counters in front of the window are zero, and zero is what the cells in
+    // front of the window hold)
+    scan_piece(a0 & ~(int64_t)3, a1, bd.gen, cg.flags);
+    if (b1 <= b0) { // one piece: everything outside it in one launch
+        const int64_t n1 = g.ncell + 1, quads = ((a0 + 3) >> 2) + ((n1 - std::min(n1, (a1 + 1 + 3) & ~(int64_t)3) + 3) >> 2) + 1;
+        hipLaunchKernelGGL(k_fill_outside, dim3(grid_for(quads, 256)), dim3(256), 0, st, cg.cell_start, a0, a1, n1, cg.cell_start + a1);
+    } else {
+        // second piece: offsets start at the first piece's total, which sits on the device in cell_start[a1]
+        fill_from(st, cg.cell_start, a1 + 1, b0, cg.cell_start + a1);
+        scan_piece(b0, b1, next_scan_gen(), nullptr);
+        hipLaunchKernelGGL(k_add_from, dim3(grid_for(b1 - b0 + 1, 256)), dim3(256), 0, st, cg.cell_start, b0, b1 + 1, cg.cell_start + a1, (int64_t)-1);
+        // behind the window: the number of atoms BINNED (cell_start[b1], on the device) — N unless the promise was broken; with
+        // the constant N a cell behind a broken window spanned the records [n_binned, N), which k_scatter / k_gather never wrote
+        if (b1 < g.ncell)
+            fill_from(st, cg.cell_start, b1 + 1, g.ncell + 1, cg.cell_start + b1);
+    }
+    return MDH_OK;
+}
+
+// every cell's atoms into descending id (or key) order
+static void sort_cells(const GridBuild &bd, CellGrid &cg)
+{
+    const Grid &g = cg.g;
+    const GridPlan &pl = bd.pl;
+    int *rank = reinterpret_cast<int *>(bd.ent); // (free once the atoms are scattered)
+    const int64_t plane = (int64_t)g.nc[1] * g.nc[2];
+    auto piece = [&](int64_t from, int64_t to) {
+        hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((to - from) * plane, 256)), dim3(256), 0, bd.st, cg.cell_start + from * plane, cg.order, (to - from) * plane, bd.rq.sort_key, rank);
+    };
+    switch (pl.sort) {
+    case GridPlan::SORT_NONE: break;
+    case GridPlan::SORT_DENSE:
+        hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, bd.st, cg.cell_start, cg.order, g.ncell, rank);
+        break;
+    case GridPlan::SORT_CELLS:
+        // (hist: this build could have been a slot build — it reports a cell of more than SLOT_CAP atoms as one would)
+        hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, bd.st, cg.cell_start, cg.order, g.ncell, bd.rq.sort_key, rank, bd.ctl, bd.gen, bd.hist);
+        if (bd.hist) { cg.big_stamp = bd.ctl + 3; cg.big_gen = bd.gen; cg.big_sink = bd.hist; }
+        break;
+    case GridPlan::SORT_PIECES:
+        piece(pl.p0, pl.p1);
+        if (pl.p3 > pl.p2) piece(pl.p2, pl.p3);
+        break;
+    }
+}
+
+// the atoms in the plan's form
+static void gather_atoms(const GridBuild &bd, CellGrid &cg)
+{
+    const int64_t N = bd.N;
+    // (the atoms binned = the grid's total, on the device: all N unless absent atoms were handed in or a window's promise was broken)
+    const int *n_binned = cg.cell_start + cg.g.ncell;
+    if (bd.pl.form == GridPlan::INDIRECT) { cg.ix = bd.x; cg.iy = bd.y; cg.iz = bd.z; cg.imv = bd.mv; } // nothing is gathered
+    else if (bd.pl.form == GridPlan::RECORDS_MOVED) hipLaunchKernelGGL(k_gather_records, dim3(grid_for(N, 256)), dim3(256), 0, bd.st, bd.rec, cg.order, cg.pk, N, n_binned);
+    else hipLaunchKernelGGL(k_gather, dim3(grid_for(N, 256)), dim3(256), 0, bd.st, bd.x, bd.y, bd.z, cg.order, cg.xs, cg.ys, cg.zs, N, bd.mv, cg.mvs, cg.pk, cg.flags + 4, n_binned);
 }
 
 int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b, const GridRequest &rq,
                     CellGrid &cg)
 {
-    PendingWindows hints; // (from here on values: only a build for neighbor rows uses them, below)
+    PendingWindows hints; // (from here on values: only a build for neighbor rows uses them, plan_grid)
     MDH_TRY(take_pending_windows(hints));
-    const CellWindow &window = hints.cells, &centre = hints.centre;
-    const bool packed = rq.atoms != GridRequest::SORTED_ARRAYS;
-    bool scattered = rq.atoms == GridRequest::FOR_ROWS_UNORDERED;
-    const Grid &g = cg.g;
-    hipStream_t st = sc.stream();
+    const Grid g = cg.g;
+    cg = CellGrid{};
+    cg.g = g;
+    cg.n_binned = N;
 
-    cg.xs = cg.ys = cg.zs = nullptr;
-    cg.mvs = nullptr;
-    cg.pk = nullptr;
-    cg.ix = cg.iy = cg.iz = nullptr;
-    cg.imv = nullptr;
-    cg.slot_cap = 0; cg.spill = nullptr; cg.n_spill = nullptr; cg.n_binned = N;
-    cg.big_stamp = nullptr; cg.big_gen = 0; cg.big_sink = nullptr;
-    // a build for rows: the one lookup of the signature's record; the passes over the grid reach it through cg.fb
-    cg.fb = nullptr;
-    if (packed && rq.slots_ok) MDH_TRY(grid_feedback(N, g.ncell, &cg.fb));
-    const int row_width = rq.row_width < 0 ? (cg.fb ? cg.fb->width.load(std::memory_order_relaxed) : 0) : rq.row_width;
-    // what the atoms are wanted as — decided before anything is allocated: a slot grid has no entries, no prefix array and
-    // counters of its own
-    // scattered (FOR_ROWS_UNORDERED): the caller knows that the atoms come in no spatial order
-    int *rec_flag = nullptr;
-    bool indirect = false;
-    if (packed) {
-        // records: always for a caller that knows (scattered); for a large system otherwise when the last sample of this (N, grid) said so
-        if (!scattered && N >= (int64_t(1) << 18)) {
-            const OrderHint h = order_hint(1, N, g.ncell, x);
-            scattered = h.word && *(volatile int *)h.word != 0;
-            if (h.word && h.sample) rec_flag = h.word;
-        }
-        // input in some spatial order: no sorted copy, the kernels read through `order` (CellGrid::ix); MDH_INDIRECT=0 /
-        // mdh_debug_set_indirect(0): the records always — an A/B switch, and how the tests reach both paths on one input
-        // (not for dense cells — six atoms and more, the wide instance's ground: two workgroups per CU hide the staging's
-        // dependent gathers badly, build_neighbor(5.0, 50) at 10 M atoms 4.48 -> 4.60 ms; profiles/r06_cell_grid_ab.txt)
-        indirect = g_indirect.load(std::memory_order_relaxed) != 0 && !scattered && rq.sort_desc && (double)N <= 6.0 * (double)g.ncell && row_width <= 16;
-    }
-    // The slot grid (CellGrid::slot_cap) where the rule allows.  What the rule asks of the signature's history comes from two
-    // pinned words of its record: the in-cell sort of every build that could have been a slot build stamps one with its generation
-    // when it sees a cell of more than SLOT_CAP atoms (GridFeedback::BIG), and the tile kernel's mop-up reports the tiles it was left
-    // (GridFeedback::LISTED).  Both arrive when the device gets there: a build that reads an old answer is a slower one, never a wrong one.
-    int *hist = nullptr; // != nullptr: this build keeps the history (the record's two words from BIG on)
-    bool slot = false;
-    const bool windows = window.set || centre.set;
-    if (cg.fb && slot_grid_rule(indirect, rq.sort_key != nullptr, windows, row_width, g.ncell, N, true, false, 0)) {
-        hist = cg.fb->host + GridFeedback::BIG;
+    GridPlanIn in;
+    int *order_word = nullptr;
+    MDH_TRY(read_plan_inputs(rq, N, b, x, hints, cg, in, &order_word));
+    GridBuild bd{sc.stream(), x, y, z, N, b, rq, plan_grid(in)};
+    const GridPlan &pl = bd.pl;
+    g_last_form.store(pl.form, std::memory_order_relaxed);
+    if (pl.keeps_history) {
+        bd.hist = cg.fb->host + GridFeedback::BIG;
         g_last_hist.store(cg.fb, std::memory_order_relaxed);
-        const int last = *(volatile int *)hist, listed = ((volatile int *)cg.fb->host)[GridFeedback::LISTED];
-        const bool seen = last >= 0, big = last > 0;
-        slot = g_slot_grid.load(std::memory_order_relaxed) != 0 && (g_slot_force ||
-               slot_grid_rule(indirect, rq.sort_key != nullptr, windows, row_width, g.ncell, N, seen, big, listed));
     }
-    // bin counters in a kept block (all zero whenever idle: the scan clears what it reads), the scan's control words in
-    // another; the eight device flags are plain scratch, written by the scan — a build enqueues no hipMemsetAsync
-    // (a slot build: the half of a KEEP_SLOT block that the previous slot build's sort cleared, 64 words of header — [0] the length
-    // of the spill list — and the counters behind them)
-    unsigned *cell_count = nullptr, *slot_block = nullptr, *slot_idle = nullptr;
-    int64_t slot_idle_n = 0;
-    SlotBlock *sb = nullptr;
-    if (slot) {
-        // (+ 64 words behind the counts: the tile kernel reads a cell's count with the word behind it)
-        slot_block = static_cast<unsigned *>(sc.alloc_kept(2 * sizeof(unsigned) * (size_t)(g.ncell + 128), Scope::KEEP_SLOT));
-        if (slot_block) {
-            const size_t half = sc.held_bytes(slot_block) / 8; // words of a half (a block is a multiple of 256 bytes)
-            sb = slot_block_state(slot_block);
-            cell_count = slot_block + (size_t)sb->next * half + 64;
-            slot_idle = slot_block + (size_t)(1 - sb->next) * half;
-            slot_idle_n = std::min<int64_t>(sb->dirty[1 - sb->next], (int64_t)half); // (a freed block's address may come back as a smaller, zero-filled one)
-        }
-    } else {
-        cell_count = static_cast<unsigned *>(sc.alloc_kept(sizeof(unsigned) * (size_t)g.ncell, Scope::KEEP_ZERO));
-    }
-    unsigned *ctl = static_cast<unsigned *>(sc.alloc_kept(scan_ctl_bytes(g.ncell), Scope::KEEP_SCAN));
-    cg.flags = sc.alloc_n<int>(8);
-    cg.cell_start = slot ? reinterpret_cast<int *>(cell_count) : sc.alloc_n<int>((size_t)g.ncell + 1);
-    int2 *ent = sc.alloc_n<int2>((size_t)N); // (cell, slot) of every atom: k_assign -> k_scatter; a slot build: its spill list
-    int *rank = reinterpret_cast<int *>(ent); // ... and, once the atoms are scattered, the N ints of scratch of the in-cell sorts
-    // (four spare entries: the tile kernel reads a cell's first four ids as one 16-byte request)
-    cg.order = sc.alloc_n<int>(slot ? (size_t)g.ncell * SLOT_CAP + 4 : (size_t)N + 4);
-    const int64_t slot_hi = 4 * g.ncell; // (a slot grid: where the second plane of four slots per cell starts)
-    unsigned short *mv = sc.alloc_n<unsigned short>((size_t)N);
-    CellGrid::Packed *rec = nullptr;
-    if (packed) {
-        if (!indirect) cg.pk = sc.alloc_n<CellGrid::Packed>((size_t)N);
-        if (scattered) rec = sc.alloc_n<CellGrid::Packed>((size_t)N);
-    } else {
-        cg.xs = sc.alloc_n<double>((size_t)N);
-        cg.ys = sc.alloc_n<double>((size_t)N);
-        cg.zs = sc.alloc_n<double>((size_t)N);
-        cg.mvs = sc.alloc_n<unsigned short>((size_t)N);
-    }
-    if (sc.failed())
-        return sc.error();
+    MDH_TRY(allocate_grid(sc, bd, cg));
 
-    // window of planes along axis 0 (orthogonal boxes, rc-wide cells): [p0, p1) and, when it wraps around the ring, [p2, p3)
-    int p0 = 0, p1 = g.nc[0], p2 = 0, p3 = 0;
-    bool windowed = false;
-    if (window.set) {
-        const CellWindow &w = window;
-        // (only the neighbor builds — the callers of the packed record — know what a window leaves undone; a hint that meets
-        // any other grid build is dropped)
-        if (packed && w.axis == 0 && !b.tri && g.mode == 0 && g.nc[0] >= 16 && w.hi > w.lo && w.hi - w.lo < 0.75) {
-            const double L = b.h[0];
-            int lo = (int)std::floor(w.lo * L * g.rc_inv) - 1, hi = (int)std::ceil(w.hi * L * g.rc_inv) + 1; // one plane of margin
-            if (hi - lo < g.nc[0] - 2) {
-                windowed = true;
-                if (lo < 0) { p0 = 0; p1 = std::min(hi, g.nc[0]); p2 = g.nc[0] + lo; p3 = g.nc[0]; }         // wraps below
-                else if (hi > g.nc[0]) { p0 = 0; p1 = hi - g.nc[0]; p2 = lo; p3 = g.nc[0]; }                   // wraps above
-                else { p0 = lo; p1 = hi; p2 = p3 = 0; }
-                if (p2 < p1 && p3 > p2) { windowed = false; p0 = 0; p1 = g.nc[0]; p2 = p3 = 0; }               // (the pieces meet: everything)
-            }
-        }
-    }
-    const int64_t plane = (int64_t)g.nc[1] * g.nc[2];
-    cg.win_lo = cg.win_hi = 0;
-    if (windowed && p3 <= p2) { cg.win_lo = p0; cg.win_hi = p1; } // one piece: the tile kernel runs over its range of tiles
-    cg.cen_lo = cg.cen_hi = 0;
-    if (centre.set) {
-        const CellWindow &c = centre;
-        if (packed && c.axis == 0 && !b.tri && g.mode == 0 && c.hi > c.lo && c.lo >= 0.0 && c.hi <= 1.0) {
-            // the planes an atom of fraction [lo, hi) can be binned into (cell_coords: floor((x - o) rc_inv), clamped); the ends moved
-            // out by 1e-9 of their value — far more than the roundings that separate the caller's fraction of an atom from the grid's
-            // (x - o) rc_inv, far less than a plane: an atom ON the slab's face is inside whichever way it was rounded
-            const double L = b.h[0];
-            cg.cen_lo = std::max(0, std::min(g.nc[0] - 1, (int)std::floor(c.lo * L * g.rc_inv * (1.0 - 1e-9) - 1e-9)));
-            cg.cen_hi = std::min(g.nc[0], (int)std::floor(c.hi * L * g.rc_inv * (1.0 + 1e-9) + 1e-9) + 1);
-        }
-    }
+    cg.win_lo = pl.win_lo; cg.win_hi = pl.win_hi;
+    cg.cen_lo = pl.cen_lo; cg.cen_hi = pl.cen_hi;
     cg.flags_fresh = true;
-    // slack for the raw-vs-wrapped consistency flag: far above rounding, far below a cell width
-    const double slack = 0.01 / (g.rc_inv > 0 ? g.rc_inv : 1.0);
-    // the promise is checked where the atoms are binned (a word of pinned host memory the kernel writes) and read by the next
-    // build of this thread or by mdh_cell_window_check
-    CellPlanes win{p0, p1, p2, p3, nullptr};
-    if (windowed) {
+    if (pl.windowed) {
         if (!g_window_violations) MDH_HIP(hipHostMalloc(reinterpret_cast<void **>(&g_window_violations), sizeof(int), hipHostMallocDefault));
         *g_window_violations = 0;
-        win.bad = g_window_violations;
+        bd.bad = g_window_violations;
     }
-    if (rec_flag) {
-        const double *h = b.h;
-        const double vol = std::fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]));
-        const double edge = std::cbrt(64.0 * vol / (double)N);
-        double nb[3];
-        for (int d = 0; d < 3; ++d) nb[d] = std::max(1.0, std::floor(b.thick[d] / edge));
-        hipLaunchKernelGGL(k_order_far_flag, dim3(1), dim3(1024), 0, st, x, y, z, N, b, nb[0], nb[1], nb[2], rec_flag);
-    }
-    const unsigned gen = next_scan_gen(); // stamps of this build's k_assign; the (first) scan below is launched with the same value
-    // atoms per lane: four; small systems keep one atom per lane (they need the workgroups to fill the chip)
-    // (measured at 10 M atoms, with the grouping of round 5 — runs of adjacent lanes: 145 -> 120 us on a lattice, 162 -> 162 on a polycrystal — 10 M runs of one atom, the atomics' own
-    // throughput — 413 -> 440 on a shuffled frame, which therefore keeps one: profiles/r05_assign_k.txt)
-    const bool assign4 = N >= (int64_t)1 << 20 && !scattered;
-#define MDH_ASSIGN(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)rq.wrap_first, ent, cell_count, ctl, gen, slack, mv, win, rec, packed ? 1 : 0)
-#define MDH_ASSIGN_SLOT(TRI, K) hipLaunchKernelGGL((k_assign<TRI, K, true>), dim3(grid_for(N, 256 * K)), dim3(256), 0, st, x, y, z, N, b, g, (int)rq.wrap_first, (int2 *)nullptr, cell_count, ctl, gen, slack, mv, win, rec, 1, cg.order, ent, cell_count - 64, slot_hi)
-    if (slot) {
-        // bin, sort in place, done: no scan, no scatter, no gather (the atoms stay where the caller has them, CellGrid::ix)
-        if (b.tri) { if (assign4) MDH_ASSIGN_SLOT(true, 4); else MDH_ASSIGN_SLOT(true, 1); }
-        else { if (assign4) MDH_ASSIGN_SLOT(false, 4); else MDH_ASSIGN_SLOT(false, 1); }
-        hipLaunchKernelGGL(k_sort_slots, dim3(grid_for(std::max<int64_t>(g.ncell, slot_idle_n), 256)), dim3(256), 0, st, cell_count, cg.order, g.ncell,
-                           slot_idle, slot_idle_n, ctl, gen, hist, cg.flags, slot_hi);
-        MDH_HIP(hipGetLastError());
-        {
-            std::lock_guard<std::mutex> lk(g_slot_mu);
-            sb->dirty[1 - sb->next] = 0;          // cleared by the sort above
-            sb->dirty[sb->next] = g.ncell + 64;   // this build's header and counts: read until the next slot build's sort clears them
-            sb->next = 1 - sb->next;
-        }
-        sc.keep_confirm(slot_block);
-        cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist;
-        cg.slot_cap = SLOT_CAP;
-        cg.slot_hi = slot_hi;
-        cg.spill = ent;
-        cg.n_spill = cell_count - 64;
-        cg.ix = x; cg.iy = y; cg.iz = z; cg.imv = mv;
-        g_last_slot_build = 1;
-        return MDH_OK;
-    }
-    g_last_slot_build = 0;
-    if (b.tri) {
-        if (assign4) MDH_ASSIGN(true, 4); else MDH_ASSIGN(true, 1);
-    } else {
-        if (assign4) MDH_ASSIGN(false, 4); else MDH_ASSIGN(false, 1);
-    }
-#undef MDH_ASSIGN
-#undef MDH_ASSIGN_SLOT
-    auto scan_piece = [&](int64_t from, int64_t to, unsigned use_gen, int *flags) {
-        launch_scan_gen(st, cell_count + from, cg.cell_start + from, to - from, ctl, use_gen, true, flags); // [to] = the piece's total
-    };
-    if (!windowed) {
-        scan_piece(0, g.ncell, gen, cg.flags);
-    } else {
-        // the pieces in index order: [p0, p1) then [p2, p3); a piece is scanned on its own, the atoms before it added by the
-        // fill / by a second add pass; cell_start elsewhere = what a full scan leaves: the atoms binned so far.  The counters
-        // outside the window are zero (kept block; atoms out there take no slot) and stay untouched.
-        const int64_t a0 = p0 * plane, a1 = p1 * plane, b0 = p2 * plane, b1 = p3 * plane;
-        // (constant fills through the runtime's fill kernel: 16-byte stores, 5 us per 10 MB against 15 of a store per thread)
-        hipError_t fill_err = hipSuccess;
-        auto fill_const = [&](int64_t from, int64_t to, int v) {
-            if (to > from && fill_err == hipSuccess)
-                fill_err = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cg.cell_start + from), v, (size_t)(to - from), st);
-        };
-        if (b1 > b0) fill_const(0, a0, 0);
-        // (from a multiple of four cells on: the scan moves 16 bytes per access only from an aligned start — 66 against 26 us for the
-        // 3.6 M cells of a 10 M-atom slab; the up to three counters in front of the window are zero, and zero is what the cells in
-        // front of the window hold)
-        scan_piece(a0 & ~(int64_t)3, a1, gen, cg.flags);
-        if (b1 <= b0) { // one piece: everything outside it in one launch
-            const int64_t n1 = g.ncell + 1, quads = ((a0 + 3) >> 2) + ((n1 - std::min(n1, (a1 + 1 + 3) & ~(int64_t)3) + 3) >> 2) + 1;
-            hipLaunchKernelGGL(k_fill_outside, dim3(grid_for(quads, 256)), dim3(256), 0, st, cg.cell_start, a0, a1, n1, cg.cell_start + a1);
-        } else if (b1 > b0) {
-            // second piece: offsets start at the first piece's total, which sits on the device in cell_start[a1]
-            fill_from(st, cg.cell_start, a1 + 1, b0, cg.cell_start + a1);
-            scan_piece(b0, b1, next_scan_gen(), nullptr);
-            hipLaunchKernelGGL(k_add_from, dim3(grid_for(b1 - b0 + 1, 256)), dim3(256), 0, st, cg.cell_start, b0, b1 + 1, cg.cell_start + a1, (int64_t)-1);
-            // behind the window: the number of atoms BINNED (cell_start[b1], on the device) — N unless the promise was broken; with
-            // the constant N a cell behind a broken window spanned the records [n_binned, N), which k_scatter / k_gather never wrote
-            if (b1 < g.ncell)
-                fill_from(st, cg.cell_start, b1 + 1, g.ncell + 1, cg.cell_start + b1);
-        }
-        MDH_HIP(fill_err);
-    }
-    sc.keep_confirm(cell_count); // every counter a binned atom touched has been read and cleared by a scan enqueued above
-    hipLaunchKernelGGL(k_scatter, dim3(grid_for((N + 1) / 2, 256)), dim3(256), 0, st, ent, cg.cell_start, cg.order, N);
-    if (rq.sort_desc) {
-        if (!windowed && !rq.sort_key && (double)N > 6.0 * (double)g.ncell) {
-            hipLaunchKernelGGL(k_sort_cells_dense, dim3(grid_for(g.ncell, 32)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rank);
-        } else if (!windowed) {
-            // (hist: this build could have been a slot build — it reports a cell of more than SLOT_CAP atoms as one would)
-            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for(g.ncell, 256)), dim3(256), 0, st, cg.cell_start, cg.order, g.ncell, rq.sort_key, rank, ctl, gen, hist);
-            if (hist) { cg.big_stamp = ctl + 3; cg.big_gen = gen; cg.big_sink = hist; }
-        } else {
-            hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p1 - p0) * plane, 256)), dim3(256), 0, st, cg.cell_start + p0 * plane, cg.order, (p1 - p0) * plane, rq.sort_key, rank);
-            if (p3 > p2)
-                hipLaunchKernelGGL(k_sort_cells, dim3(grid_for((p3 - p2) * plane, 256)), dim3(256), 0, st, cg.cell_start + p2 * plane, cg.order, (p3 - p2) * plane, rq.sort_key, rank);
-        }
-    }
-    // (the atoms binned = the grid's total, on the device: all N unless absent atoms were handed in or a window's promise was broken)
-    const int *n_binned = cg.cell_start + g.ncell;
-    if (packed && !cg.pk) { cg.ix = x; cg.iy = y; cg.iz = z; cg.imv = mv; } // indirect: nothing is gathered
-    else if (rec) hipLaunchKernelGGL(k_gather_records, dim3(grid_for(N, 256)), dim3(256), 0, st, rec, cg.order, cg.pk, N, n_binned);
-    else hipLaunchKernelGGL(k_gather, dim3(grid_for(N, 256)), dim3(256), 0, st, x, y, z, cg.order, cg.xs, cg.ys, cg.zs, N, mv, cg.mvs, cg.pk, cg.flags + 4, n_binned);
+    if (pl.samples_order) sample_order(bd, order_word);
+    bd.gen = next_scan_gen();
+    bin_atoms(bd, cg);
+    if (bd.slot())
+        return finish_slot_grid(sc, bd, cg);
+    MDH_TRY(scan_cells(bd, cg));
+    sc.keep_confirm(bd.cell_count); // every counter a binned atom touched has been read and cleared by a scan enqueued above
+    hipLaunchKernelGGL(k_scatter, dim3(grid_for((N + 1) / 2, 256)), dim3(256), 0, bd.st, bd.ent, cg.cell_start, cg.order, N);
+    sort_cells(bd, cg);
+    gather_atoms(bd, cg);
     MDH_HIP(hipGetLastError());
     return MDH_OK;
 }
@@ -1128,6 +1163,23 @@ int mdh_debug_slot_grid_counters(int64_t *out4)
 int mdh_debug_slot_grid_rule(int ordered, int keyed, int windowed, int row_width, int64_t ncell, int64_t N, int seen, int big, int listed)
 {
     return slot_grid_rule(ordered != 0, keyed != 0, windowed != 0, row_width, ncell, N, seen != 0, big != 0, listed) ? 1 : 0;
+}
+int mdh_debug_grid_plan(const int64_t *in24, const double *in6, int *out15)
+{
+    GridPlanIn in;
+    in.atoms = (int)in24[0]; in.sort_desc = in24[1] != 0; in.keyed = in24[2] != 0; in.slots_ok = in24[3] != 0; in.row_width = (int)in24[4];
+    in.N = in24[5]; in.ncell = in24[6]; in.nc[0] = (int)in24[7]; in.nc[1] = (int)in24[8]; in.nc[2] = (int)in24[9];
+    in.mode = (int)in24[10]; in.tri = in24[11] != 0;
+    in.cells = CellWindow{(int)in24[13], in6[2], in6[3], in24[12] != 0};
+    in.centre = CellWindow{(int)in24[15], in6[4], in6[5], in24[14] != 0};
+    in.order_word = (int)in24[16]; in.order_sample = in24[17] != 0; in.big = (int)in24[18]; in.listed = (int)in24[19]; in.record_width = (int)in24[20];
+    in.indirect_on = in24[21] != 0; in.slot_on = in24[22] != 0; in.slot_force = in24[23] != 0;
+    in.rc_inv = in6[0]; in.h0 = in6[1];
+    const GridPlan pl = plan_grid(in);
+    const int out[15] = {pl.form, pl.keeps_history, pl.samples_order, pl.assign4, pl.p0, pl.p1, pl.p2, pl.p3, pl.windowed, pl.win_lo, pl.win_hi,
+                         pl.cen_lo, pl.cen_hi, pl.sort, pl.row_width};
+    std::copy(out, out + 15, out15);
+    return MDH_OK;
 }
 }
 

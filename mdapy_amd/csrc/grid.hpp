@@ -1,6 +1,7 @@
 // grid.hpp — the rc-wide cell grid shared by the neighbor build, kNN and RDF kernels.
 #pragma once
 #include "common.hpp"
+#include "grid_plan.hpp"
 #include <atomic>
 #include <cmath>
 
@@ -37,24 +38,24 @@ __host__ __device__ __forceinline__ int axis(int code, int d) { return ((code >>
 struct GridFeedback;
 // device buffers produced by build_cell_grid, cell_grid.hip (owned by the Scope that built them)
 struct CellGrid {
-    Grid g;
+    Grid g{};
     GridFeedback *fb = nullptr; // a build for neighbor rows (GridRequest::slots_ok): what the builds of its signature leave for the next one
     int win_lo = 0, win_hi = 0; // planes [win_lo, win_hi) of axis 0 the grid was built over (a promised window, cell_grid.hip); 0, 0: all
     int cen_lo = 0, cen_hi = 0; // planes [cen_lo, cen_hi) of axis 0 whose atoms want rows (mdh_hint_centre_window: a slab's own atoms; the rest of the window is halo); 0, 0: all
     mutable bool flags_fresh = false; // flags[] were zeroed by build_cell_grid and nobody has used them yet (the first neighbor pass skips its own memset: every hipMemsetAsync is a 5 us launch)
-    int *cell_start; // [ncell+1] exclusive prefix of the per-cell populations
-    int *order;      // [N] atom ids, cell-major, DESCENDING id inside a cell
-    double *xs, *ys, *zs; // [N] raw positions in `order`
+    int *cell_start = nullptr; // [ncell+1] exclusive prefix of the per-cell populations
+    int *order = nullptr;      // [N] atom ids, cell-major, DESCENDING id inside a cell
+    double *xs = nullptr, *ys = nullptr, *zs = nullptr; // [N] raw positions in `order`
     // device flags written while binning:
     //   flags[0] != 0 : some atom's raw coordinate differs from its wrapped one by more than `slack` on a
     //                   periodic axis (unwrapped input) -> per-cell image shifts are not valid
     //   flags[1]      : largest cell population
-    int *flags;
-    unsigned short *mvs; // [N] per-atom image code (raw vs wrapped coordinate; img::), in `order`
+    int *flags = nullptr;
+    unsigned short *mvs = nullptr; // [N] per-atom image code (raw vs wrapped coordinate; img::), in `order`
     // [N] the same five values as one 32-byte record per atom (neighbor builds): the tile kernel stages an atom with two
     // 16-byte requests instead of five small ones
     struct Packed { double x, y, z; int id, code; };
-    Packed *pk; // when set, xs / ys / zs / mvs are NOT filled (ensure_unpacked() does that for the kernels that want them)
+    Packed *pk = nullptr; // when set, xs / ys / zs / mvs are NOT filled (ensure_unpacked() does that for the kernels that want them)
     // INDIRECT (neighbor builds of input that comes in some spatial order): no sorted copy of the atoms at all — atom q of the cell
     // order is atom order[q] of the CALLER's arrays (ix, iy, iz; image code imv[order[q]] when flags[4] says that any atom has
     // one).  pk, xs, ys, zs, mvs are all null; the kernels read through `order` (the tile kernel stages a cell's atoms with four
@@ -79,8 +80,6 @@ struct CellGrid {
     unsigned big_gen = 0;
     int *big_sink = nullptr;
 };
-// atoms a cell of a slot grid holds in place (two planes of four ids, slot_pos)
-constexpr int SLOT_CAP = 8;
 // position in CellGrid::order of slot k (< SLOT_CAP) of cell c; hi: CellGrid::slot_hi
 __host__ __device__ __forceinline__ int64_t slot_pos(int64_t c, int k, int64_t hi) { return c * 4 + k + (k >= 4 ? hi - 4 : 0); }
 // the second plane and the spill list of a slot grid, as the thread-per-atom kernels see them (CellView below)
@@ -392,16 +391,13 @@ struct GridRequest {
     // wide instance, which hides the indirect staging's gathers badly (two or three workgroups per CU): such a build keeps the
     // records (the 12-nearest search's cutoff build, 4.7 atoms per cell, rows of 24: 2.15 ms with records, 2.22 without)
     int row_width = 0;
-    // FOR_ROWS: the atoms may also be wanted as a SLOT GRID (CellGrid::slot_cap) where slot_grid_rule() allows: every kernel behind
+    // FOR_ROWS: the atoms may also be wanted as a SLOT GRID (CellGrid::slot_cap) where slot_grid_rule() (grid_plan.hpp) allows: every kernel behind
     // neighbor_pass reads both forms
     bool slots_ok = false;
 };
-// cell_grid.hip: may this build bin straight into cell slots?  (host only; exported as mdh_debug_slot_grid_rule for the table test)
-// ordered: the ix form would be taken; keyed: a sort_key; windowed: a pending cell or centre window; seen: a build of this (N, grid)
-// has reported; big: that build saw a cell of more than SLOT_CAP atoms; listed: tiles it listed (-1: not known)
-bool slot_grid_rule(bool ordered, bool keyed, bool windowed, int row_width, int64_t ncell, int64_t N, bool seen, bool big, int listed);
-// Bins the atoms into cg.g (dims/mode set by the caller) and produces cell_start/order and the atoms as rq.atoms says; takes the
-// thread's pending window hints (mdh_hint_cell_window, mdh_hint_centre_window), whatever the build is for
+// Bins the atoms into cg.g (dims/mode set by the caller: all the build keeps of cg) and produces cell_start/order and the atoms in
+// the form plan_grid (grid_plan.hpp) picks for rq; takes the thread's pending window hints (mdh_hint_cell_window,
+// mdh_hint_centre_window), whatever the build is for
 int build_cell_grid(Scope &sc, const double *x, const double *y, const double *z, int64_t N, const DBox &b, const GridRequest &rq,
                     CellGrid &cg);
 
