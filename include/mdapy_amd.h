@@ -484,6 +484,27 @@ int mdh_atomic_strain(const int *verlet, const int *nn, int64_t N, int64_t M, co
                       const double *ref_z, const double *cur_x, const double *cur_y, const double *cur_z, const double *map9_host,
                       double *shear, double *volumetric, int space, void *stream);
 
+/* ---- _eam --------------------------------------------------------------- */
+/* replaces _eam.EAM.calculate                                src/eam.cpp:54-183
+ * Embedded-atom energies (N) f64, forces (N x 3) f64 and virials (N x 9) f64 over a cutoff list (verlet, dist N x M; nn N) of
+ * atoms with types 0 .. nelem-1 (type N, i32).  Two passes over the rows in list order, entries with dist > rc skipped, a row
+ * ending at nn[i] entries or at the first entry outside [0, N): the density of every atom from the list's distances and the
+ * embedding energy and its derivative, then the pair terms with the minimum image of box9 / origin3 / boundary3 (host arrays).
+ * accumulate != 0: energy = (energy + F) + e_pair, force += f, virial += v * 0.5, as the reference adds into its arrays;
+ * accumulate == 0: the same with 0.0 for what the arrays held (they need not be initialised).
+ * The splines are knots of the reference's UniformCubicSpline (src/spline.h:394-500), computed by the caller: 4 f64
+ * (a, b, c, d) per grid point, F_knots (nelem x nrho x 4) over the density with spacing drho, rho_knots (nelem x nr x 4) and
+ * rphi_knots (nelem x nelem x nr x 4, r * phi of the pair (t_i, t_j)) over the distance with spacing dr.  They live where the
+ * other arrays live (space).  An atom whose type is outside [0, nelem) contributes nothing to others and receives nothing
+ * itself (accumulate: its rows are left alone; otherwise they are 0).
+ * virial_sum9 (9 f64, same space; NULL: not wanted): the column sums of the first n_real rows of virial after the call, added in
+ * a fixed two-level order without atomics — the same bits on every run.
+ * MDH_ERR_ARG before any device work: nelem < 1, nr < 2, nrho < 2, dr, drho or rc not positive, M >= 2^23, n_real outside [0, N]. */
+int mdh_eam(const double *x, const double *y, const double *z, const int *type, int64_t N, const double *box9, const double *origin3,
+            const int *boundary3, const int *verlet, const double *dist, const int *nn, int64_t M, const double *F_knots,
+            const double *rho_knots, const double *rphi_knots, int nelem, int nrho, double drho, int nr, double dr, double rc,
+            int accumulate, double *energy, double *force, double *virial, int64_t n_real, double *virial_sum9, int space, void *stream);
+
 /* ---- _chill_plus ------------------------------------------------------ */
 /* replaces _chill_plus.compute_chill_plus                   src/chill_plus.cpp:76-179
  * CHILL+ (Nguyen & Molinero 2015) over a cutoff list: an entry jj < nn[i] is a bond iff dist[i, jj] <= rc and verlet[i, jj] >= 0.

@@ -16,6 +16,8 @@ from .polyhedral_template_matching import PolyhedralTemplateMatching
 from .radial_distribution_function import RadialDistributionFunction
 from .warren_cowley_parameter import WarrenCowleyParameter
 from .atomic_strain import AtomicStrain
+from .calculator import CalculatorMP
+from .eam import EAM
 from .chill_plus import ChillPlus
 from .wigner_seitz_defect import WignerSeitzAnalysis
 from .lindemann_parameter import LindemannParameter
@@ -31,7 +33,7 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
+    "AtomicStrain", "CalculatorMP", "EAM", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
     "Trajectory", "unwrap_trajectory", "VDW_RADII", "vdw_radius",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

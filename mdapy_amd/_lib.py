@@ -100,6 +100,8 @@ _SIGNATURES = {
     "mdh_strain_pack": [vp, vp, vp, i64, vp, vp, cint, vp],
     "mdh_atomic_strain_records": [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
     "mdh_atomic_strain": [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_eam": [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, cint, cint, dbl, cint, dbl, dbl, cint, vp, vp, vp, i64, vp,
+                cint, vp],
     "mdh_chill_plus": [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, dbl, vp, cint, vp],
     "mdh_wcp": [vp, vp, vp, i64, i64, cint, vp, cint, vp],
     "mdh_wcp_counts": [vp, vp, vp, vp, i64, i64, cint, vp, cint, vp],

@@ -393,6 +393,7 @@ void warm_sbo(hipStream_t st);
 void warm_rdf(hipStream_t st);
 void warm_bond(hipStream_t st);
 void warm_strain(hipStream_t st);
+void warm_eam(hipStream_t st);
 void warm_chill(hipStream_t st);
 void warm_wcp(hipStream_t st);
 void warm_knn(hipStream_t st);
@@ -522,6 +523,7 @@ int mdh_warm(void)
     mdh::warm_rdf(nullptr);
     mdh::warm_bond(nullptr);
     mdh::warm_strain(nullptr);
+    mdh::warm_eam(nullptr);
     mdh::warm_chill(nullptr);
     mdh::warm_wcp(nullptr);
     mdh::warm_knn(nullptr);

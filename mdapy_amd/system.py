@@ -29,6 +29,7 @@ from .angular_distribution_function import AngularDistributionFunction
 from .atomic_temperature import AtomicTemperature
 from .bond_analysis import BondAnalysis
 from .box import Box
+from .calculator import CalculatorMP
 from .centro_symmetry_parameter import CentroSymmetryParameter
 from .chill_plus import ChillPlus
 from .cluster_analysis import ClusterAnalysis
@@ -293,15 +294,54 @@ class System:
         return f"Atom Number: {self.N}\n{self.box}\nParticle Information:\n{self.data}"
 
     def update_data(self, data, reset_calculator=False, reset_neighbor=False, reset_calcolator=None):
-        """replace the per-atom frame; ``reset_neighbor`` also forgets the neighbor list.  ``reset_calcolator`` is the
-        reference's deprecated misspelling of ``reset_calculator`` (system.py:686-744), accepted with the same warning; there
-        is no calculator on this path, so neither flag has anything to clear."""
+        """replace the per-atom frame; ``reset_neighbor`` also forgets the neighbor list, ``reset_calculator`` clears what the
+        attached calculator has cached (system.py:746-747).  ``reset_calcolator`` is the reference's deprecated misspelling of
+        ``reset_calculator`` (system.py:686-744), accepted with the same warning."""
         if reset_calcolator is not None:
             warnings.warn("`reset_calcolator` is a misspelling and is deprecated; use `reset_calculator` instead.",
                           DeprecationWarning, stacklevel=2)
+            reset_calculator = reset_calculator or reset_calcolator
         self._frame = Frame.from_any(data)
+        if reset_calculator and isinstance(self.calc, CalculatorMP):
+            self.calc.results = {}
         if reset_neighbor:
             self._forget_list()
+
+    # ------------------------------------------------------- the calculator (src/mdapy/system.py:247-258, 560-684)
+    _calc = None
+
+    @property
+    def calc(self):
+        return self._calc
+
+    @calc.setter
+    def calc(self, value):
+        assert isinstance(value, CalculatorMP), f"calc must be CalculatorMP, instead of {type(value).__name__}"
+        value.results = {}
+        self._calc = value
+
+    def _calculated(self, getter):
+        """what the calculator's ``getter`` says of this frame.  A calculator that works over a neighbour list (``_calculate_on``:
+        EAM) is handed the System itself first, so that it uses the list the System remembers or builds — its replica, its twin."""
+        assert isinstance(self.calc, CalculatorMP), "Must assign a calc first."
+        if not self.calc.results and hasattr(self.calc, "_calculate_on"):
+            self.calc._calculate_on(self)
+        return getattr(self.calc, getter)(self.data, self.box)
+
+    def get_energy(self):
+        return self._calculated("get_energy")
+
+    def get_energies(self):
+        return self._calculated("get_energies")
+
+    def get_force(self):
+        return self._calculated("get_forces")
+
+    def get_stress(self):
+        return self._calculated("get_stress")
+
+    def get_virials(self):
+        return self._calculated("get_virials")
 
     def _get_compute_view(self):
         """(box, frame) the remembered list's indices refer to: the replica if there is one"""
