@@ -505,6 +505,40 @@ int mdh_eam(const double *x, const double *y, const double *z, const int *type, 
             const double *rho_knots, const double *rphi_knots, int nelem, int nrho, double drho, int nr, double dr, double rc,
             int accumulate, double *energy, double *force, double *virial, int64_t n_real, double *virial_sum9, int space, void *stream);
 
+/* ---- _fire ------------------------------------------------------------ */
+/* The arithmetic of the FIRE minimizer (src/mdapy/minimizer.py:270-375 does it in numpy) on (n, 3) row-major f64 arrays; no
+ * reference counterpart in C++.  f64, no contraction.  The scalars the steps hand to one another live in a RECORD of
+ * MDH_FIRE_RECORD f64 words in the arrays' memory space: a call writes the words it computes and leaves the others alone.
+ * The term of row i of a dot product a . b is (a_x b_x + a_y b_y) + a_z b_z.  The terms are added in an order that depends on n
+ * alone: blocks of 256 consecutive rows, each halved (stride h = 128 .. 1: term k takes term k + h, absent rows are 0.0), then
+ * partial k of a second level starts from 0.0 and takes the block sums k, k + 256, .. in turn and the 256 partials are halved
+ * the same way.  No atomics: the same bits on every run and every device.  MDH_ERR_ARG: n outside [1, 2^36], a null array. */
+enum { MDH_FIRE_VF = 0, MDH_FIRE_FF = 1, MDH_FIRE_FMAX2 = 2, MDH_FIRE_VV = 3, MDH_FIRE_DRDR = 4, MDH_FIRE_ZEROS = 5, MDH_FIRE_ENERGY = 6,
+       MDH_FIRE_VIRIAL = 8 /* .. 16: where the caller may have mdh_eam put its nine virial sums */, MDH_FIRE_RECORD = 24 };
+/* record[VF] = v . f (0 when v is NULL), record[FF] = f . f, record[FMAX2] = max_i |f_i|^2 (a NaN wins). */
+int mdh_fire_dots(const double *v, const double *f, int64_t n, double *record, int space, void *stream);
+/* v = v + dt * f, after v = v * 0.0 when zero_first; record[FF] = f . f, record[VV] = v . v of the new v. */
+int mdh_fire_kick(double *v, const double *f, int64_t n, double dt, int zero_first, double *record, int space, void *stream);
+/* v = (1 - a) * v + ((a * f) / sqrt(record[FF])) * sqrt(record[VV]), element by element; use_abc: the result times abc_multiplier.
+ * record[DRDR] = dr . dr of dr = dt * v, record[ZEROS] = how many components of the new v are exactly zero. */
+int mdh_fire_mix(double *v, const double *f, int64_t n, double a, double abc_multiplier, int use_abc, double dt, double *record, int space,
+                 void *stream);
+/* dr = scale * v, limited by mode: 0 — dr = (maxstep * dr) / |dr| when |dr| = sqrt(record[DRDR]) > maxstep; 1 — first, and only when
+ * record[ZEROS] == 0, every component of v with |v| * dt > maxstep becomes (maxstep / dt) * (v / |v|) (v is rewritten); 2 — as it
+ * is.  The first n_atoms rows of dr then move the atoms: unstrained (n_atoms, 3) += dr in place when it is given, else
+ * x_out = x + dr_x (and y, z), out of place. */
+int mdh_fire_move(double *v, double *dr, int64_t n, int64_t n_atoms, double scale, double dt, double maxstep, int mode, const double *record,
+                  const double *x, const double *y, const double *z, double *x_out, double *y_out, double *z_out, double *unstrained,
+                  int space, void *stream);
+/* row times 3x3 (matrix9: host, row-major): o_k = (x m_0k + y m_1k) + z m_2k, into out_rows (n, 3) or, when that is NULL, into
+ * the three columns. */
+int mdh_fire_rowmat(const double *rows, int64_t n, const double *matrix9, double *out_rows, double *out_x, double *out_y, double *out_z,
+                    int space, void *stream);
+/* out_rows[perm[p]] = rows[p], rows of three f64; an entry of perm outside [0, n) moves nothing. */
+int mdh_fire_scatter_rows(const double *rows, const int *perm, int64_t n, double *out_rows, int space, void *stream);
+/* record[word] = the sum of n numbers, in the order above. */
+int mdh_fire_sum(const double *values, int64_t n, int word, double *record, int space, void *stream);
+
 /* ---- _chill_plus ------------------------------------------------------ */
 /* replaces _chill_plus.compute_chill_plus                   src/chill_plus.cpp:76-179
  * CHILL+ (Nguyen & Molinero 2015) over a cutoff list: an entry jj < nn[i] is a bond iff dist[i, jj] <= rc and verlet[i, jj] >= 0.

@@ -102,6 +102,13 @@ _SIGNATURES = {
     "mdh_atomic_strain": [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
     "mdh_eam": [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, cint, cint, dbl, cint, dbl, dbl, cint, vp, vp, vp, i64, vp,
                 cint, vp],
+    "mdh_fire_dots": [vp, vp, i64, vp, cint, vp],
+    "mdh_fire_kick": [vp, vp, i64, dbl, cint, vp, cint, vp],
+    "mdh_fire_mix": [vp, vp, i64, dbl, dbl, cint, dbl, vp, cint, vp],
+    "mdh_fire_move": [vp, vp, i64, i64, dbl, dbl, dbl, cint, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_fire_rowmat": [vp, i64, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_fire_scatter_rows": [vp, vp, i64, vp, cint, vp],
+    "mdh_fire_sum": [vp, i64, cint, vp, cint, vp],
     "mdh_chill_plus": [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, dbl, vp, cint, vp],
     "mdh_wcp": [vp, vp, vp, i64, i64, cint, vp, cint, vp],
     "mdh_wcp_counts": [vp, vp, vp, vp, i64, i64, cint, vp, cint, vp],

@@ -394,6 +394,7 @@ void warm_rdf(hipStream_t st);
 void warm_bond(hipStream_t st);
 void warm_strain(hipStream_t st);
 void warm_eam(hipStream_t st);
+void warm_fire(hipStream_t st);
 void warm_chill(hipStream_t st);
 void warm_wcp(hipStream_t st);
 void warm_knn(hipStream_t st);
@@ -524,6 +525,7 @@ int mdh_warm(void)
     mdh::warm_bond(nullptr);
     mdh::warm_strain(nullptr);
     mdh::warm_eam(nullptr);
+    mdh::warm_fire(nullptr);
     mdh::warm_chill(nullptr);
     mdh::warm_wcp(nullptr);
     mdh::warm_knn(nullptr);

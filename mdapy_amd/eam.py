@@ -26,7 +26,7 @@ import numpy as np
 from . import kernels, policy
 from .atomic_temperature import STANDARD_ATOMIC_WEIGHT
 from .calculator import CalculatorMP
-from .devarray import as_numpy, empty, mark_frozen
+from .devarray import HArray, as_numpy, empty, mark_frozen
 from .parallel import get_num_threads
 
 
@@ -164,6 +164,26 @@ class EAM(CalculatorMP):
 
     def _calculate_on(self, system):
         """fill ``results`` for ``system``'s frame, over the list it remembers or builds"""
+        self._to_results(system, *self._run_kernels(system))
+
+    def _calculate_device(self, system, virial_sum=None):
+        """the array-level door (what ``FIRE`` looks for): the kernels run as for ``_calculate_on`` and everything stays where they
+        left it.  -> (forces (N, 3) in the caller's atom order, cut to the N real atoms; the nine virial sums — ``virial_sum`` itself
+        when one is handed in; what ``_to_results`` turns into ``results``).  A replica's real atoms are its leading rows; a twin's rows
+        go back through its permutation where they are."""
+        raw = self._run_kernels(system, virial_sum)
+        force, perm, real = raw[1], raw[4], raw[5]
+        if perm is not None:
+            back = empty((real, 3), np.float64)
+            kernels.fire.scatter_rows(force, perm, back)
+            force = back
+        elif int(force.shape[0]) != real:
+            force = force.head(real) if isinstance(force, HArray) else force[:real]
+        return force, raw[3], raw
+
+    def _run_kernels(self, system, total=None):
+        """the first half of a calculation: the list, the replica or the twin, and the kernels.  -> (energies, forces, virials — one row
+        per atom the list was built on, in its order —, the nine virial sums of the real atoms, the twin's permutation or None, N)"""
         types = self._checked(system.data)
         shim = self._shim
         if shim is None or shim[0] is not kernels.eam:
@@ -185,9 +205,15 @@ class EAM(CalculatorMP):
                 types = self._checked(frame)
         atoms = int(rows.shape[0])
         energy, force, virial = empty(atoms, np.float64), empty((atoms, 3), np.float64), empty((atoms, 9), np.float64)
-        total = empty(9, np.float64)
+        if total is None:
+            total = empty(9, np.float64)
         shim[1].calculate(*cols, types, cell.box, cell.origin, cell.boundary, rows, dist, counts, force, virial, energy, get_num_threads(),
                           accumulate=False, n_real=real, virial_sum=total)
+        return energy, force, virial, total, perm, real
+
+    def _to_results(self, system, energy, force, virial, total, perm, real):
+        """the second half: what the kernels left, as ``results`` — numpy, the caller's atom order, the N real atoms"""
+        atoms = int(energy.shape[0])
         # (the host copies the arrays in HBM hand out are read-only; only a replica's are cut, and so copied)
         out = [as_numpy(a) if atoms == real else np.array(as_numpy(a)[:real]) for a in (energy, force, virial)]
         if perm is not None:  # row p of the twin is atom perm[p] of the caller
@@ -197,6 +223,11 @@ class EAM(CalculatorMP):
                 back[where] = a
                 out[k] = back
         self.results["energies"], self.results["forces"], self.results["virials"] = out
-        v = np.array(as_numpy(total), np.float64).reshape(3, 3)
-        stress = (-0.5 * (v + v.T) / system.box.volume).ravel()
-        self.results["stress"] = stress[[0, 4, 8, 5, 2, 1]]
+        self.results["stress"] = self._stress_of_sums(as_numpy(total), system.box.volume)
+
+    @staticmethod
+    def _stress_of_sums(total, volume):
+        """the Voigt stress from the nine virial sums of the real atoms and the real box's volume"""
+        v = np.array(total, np.float64).reshape(3, 3)
+        stress = (-0.5 * (v + v.T) / volume).ravel()
+        return stress[[0, 4, 8, 5, 2, 1]]

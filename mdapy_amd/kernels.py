@@ -22,6 +22,8 @@ from . import _csp as csp
 # (not in NAMES either: the oracle has no EAM; its tests install a restatement as kernels.eam)
 from . import _eam as eam
 from . import _fast_knn as fast_knn
+# (not in NAMES either: the oracle has no minimizer; its tests install a restatement as kernels.fire)
+from . import _fire as fire
 from . import _fccpft as fccpft
 # (not in NAMES either: the oracle has no Lindemann index; its tests install a restatement as kernels.lindemann)
 from . import _lindemann as lindemann
