@@ -145,6 +145,10 @@ int mdh_debug_grid_plan(const int64_t *in24, const double *in6, int *out15);
  * plan8 = {tile cells in x/y, in z, halo atoms per tile, LDS bytes, box full of atoms, 1000 * atoms per cell,
  * cells of the occupied region, 1 if a plan was made since the last query}; bit 8 of plan8[4]: the build's cell grid was a slot grid. */
 int mdh_debug_neighbor_plan(int *plan8);
+/* test hook (host only): the tile kernel's byte table of run offsets for a tile of txy x txy x tz cells (neighbor_lane.hip,
+ * run_offset_table): out3 = {bytes of runs 0-3, bytes of runs 4-7, the bias added to the centre's halo cell}.  MDH_ERR_ARG: the
+ * halo of such a tile has more cells than a workgroup has threads, no launch takes that shape. */
+int mdh_debug_run_offset_table(int txy, int tz, unsigned *out3);
 /* test hook: fixed-cutoff CNA (mdh_fcna, src/cna.cpp:429-506): 0 = single-precision pair tests with a decision band where the
  * box allows (default; atoms inside the band are finished with the reference's double-precision expression), 1 = the
  * double-precision kernel everywhere.  Labels are identical. */

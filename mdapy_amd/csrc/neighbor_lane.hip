@@ -53,6 +53,7 @@
 #include "grid.hpp"
 #include "cna_core.hpp"
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <type_traits>
 #include <cstdio>
@@ -95,11 +96,41 @@ static FastDiv make_fastdiv(unsigned d)
 }
 // txy, tz: tile shape in cells; by_nt2, by_nt1: divisions of a tile id by the tile counts along z and y of this launch;
 // mhz, mhxy: ceil(2^16 / (tz + 2)), ceil(2^16 / (txy + 2)) — thread id / HZ as (tid * mhz) >> 16, exact for tid < 512
-struct Shape { int txy, tz; FastDiv by_nt2, by_nt1; unsigned mhz, mhxy; };
+// ro_lo, ro_hi, ro_bias: the halo-cell offsets of the nine runs of a centre's walk as a byte table (run_offset_table)
+struct Shape { int txy, tz; FastDiv by_nt2, by_nt1; unsigned mhz, mhxy; unsigned ro_lo, ro_hi, ro_bias; };
+// Halo cell of run r relative to the centre's cell: off(r) = ((r / 3 - 1) * HXY + (r % 3 - 1)) * HZ (neighbor.cpp:147-151), a launch
+// constant between -(A2 + HZ) and A2 + HZ, A2 = HXY * HZ.  Byte r of (ro_lo, ro_hi) is e(r) = 255 - (off(8) - off(r)) for runs 0 ... 7,
+// so that e(8) = 255 is what a byte selector >= 13 of v_perm_b32 delivers (RUN8_SEL) and the one-byte instance, which knows run 8's
+// tickets by their place in the row, needs no ninth entry.  With selector bytes 1 ... 3 zero the instruction returns
+// e(r) + e(0) * 0x01010100; ro_bias = off(8) - 255 - e(0) * 0x01010100 (mod 2^32) takes both back out:
+// cell + ro_bias + perm(ro_hi, ro_lo, r) = cell + off(r).
+constexpr unsigned RUN8_SEL = 13;
+constexpr int RUN_TABLE_HALO = NW * 64; // the table's range is proved for halos of at most this many cells (one per thread)
+// off(8) - off(0) = 2 HZ (HXY + 1) and HZ HXY^2 <= RUN_TABLE_HALO give 2 * RUN_TABLE_HALO (HXY + 1) / HXY^2, largest at HXY = 3
+constexpr int RUN_TABLE_SPAN = 2 * ((RUN_TABLE_HALO * 4) / 9);
+static_assert(RUN_TABLE_SPAN == 226 && RUN_TABLE_SPAN <= 255, "a run's halo-cell offset must fit one byte");
+static int run_offset(int txy, int tz, int r) { return ((r / 3 - 1) * (txy + 2) + (r % 3 - 1)) * (tz + 2); }
+static void run_offset_table(int txy, int tz, unsigned *lo, unsigned *hi, unsigned *bias)
+{
+    const int off8 = run_offset(txy, tz, 8);
+    unsigned w[2] = {0u, 0u};
+    for (int r = 0; r < 8; ++r) {
+        const int e = 255 - (off8 - run_offset(txy, tz, r));
+        assert(e >= 255 - RUN_TABLE_SPAN && e <= 255);
+        w[r >> 2] |= (unsigned)e << (8 * (r & 3));
+    }
+    *lo = w[0];
+    *hi = w[1];
+    *bias = (unsigned)(off8 - 255) - (w[0] & 255u) * 0x01010100u;
+}
 static Shape make_shape(int txy, int tz, int nt1, int nt2)
 {
-    return Shape{txy, tz, make_fastdiv((unsigned)nt2), make_fastdiv((unsigned)nt1), (65536u + (unsigned)tz + 1u) / ((unsigned)tz + 2u),
-                 (65536u + (unsigned)txy + 1u) / ((unsigned)txy + 2u)};
+    assert(txy >= 1 && tz >= 1 && (txy + 2) * (txy + 2) * (tz + 2) <= RUN_TABLE_HALO);
+    assert(2 * run_offset(txy, tz, 8) <= RUN_TABLE_SPAN);
+    Shape s{txy, tz, make_fastdiv((unsigned)nt2), make_fastdiv((unsigned)nt1), (65536u + (unsigned)tz + 1u) / ((unsigned)tz + 2u),
+            (65536u + (unsigned)txy + 1u) / ((unsigned)txy + 2u), 0u, 0u, 0u};
+    run_offset_table(txy, tz, &s.ro_lo, &s.ro_hi, &s.ro_bias);
+    return s;
 }
 typedef __attribute__((address_space(3))) unsigned char lds_byte;
 typedef int Int4 __attribute__((ext_vector_type(4))); // 16 bytes of a row (nontemporal vector stores take clang vector types)
@@ -268,6 +299,16 @@ __device__ __forceinline__ bool sqrt_fast_ok(double x)
 {
     return x >= 0x1p-767 && x < 0x1p+1000;
 }
+// the same for four arguments at once.  The range is one of the HIGH WORD of the double read as an unsigned number: biased
+// exponent 1023 - 767 = 256 up to, not including, 1023 + 1000 = 2023; a set sign bit (negative numbers, -0), inf and NaN lie
+// above it, 0 and the small numbers below.  Smallest and largest of the four words, two compares.
+__device__ __forceinline__ bool sqrt_fast_ok4(const double (&x)[4])
+{
+    const unsigned h0 = (unsigned)__double2hiint(x[0]), h1 = (unsigned)__double2hiint(x[1]), h2 = (unsigned)__double2hiint(x[2]),
+                   h3 = (unsigned)__double2hiint(x[3]);
+    const unsigned lo = min(min(min(h0, h1), h2), h3), hi = max(max(max(h0, h1), h2), h3);
+    return lo >= (256u << 20) && hi < (2023u << 20);
+}
 __device__ __forceinline__ double sqrt_fast(double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -352,6 +393,14 @@ __device__ __forceinline__ int bit_select(int m, int a, int b) // (a & m) | (b &
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(m), "v"(a), "v"(b));
     return d;
 }
+__device__ __forceinline__ unsigned and_not(unsigned m, unsigned clear) // m & ~clear, spelled out for the same reason
+{
+    unsigned d;
+    asm("v_bfi_b32 %0, %1, 0, %2" : "=v"(d) : "v"(clear), "v"(m));
+    return d;
+}
+// the top `len` bits of m (len 0 ... 31; 0 keeps nothing): a shift and one bitwise select
+__device__ __forceinline__ unsigned keep_top(unsigned m, int len) { return and_not(m, 0xffffffffu >> len); }
 __device__ __forceinline__ void quad_transpose(int (&P)[4][4], int odd1, int odd2)
 {
 #pragma unroll
@@ -467,7 +516,9 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
     const int per = (nlive + 7) / 8;
     if (parent && listed_sink && blockIdx.x == 0 && tid == 0)
         *listed_sink = min(*n_live, nt0 * nt1 * parent_nt2); // (pinned host memory: the next build sizes this pass's grid with it)
-    struct Tile { int id, T0, T1, T2; bool empty; };
+    // interior: the whole halo lies inside the grid, away from every seam and every open face — no wrap, no image, no edge cell
+    // (c0: its first cell).  Workgroup-uniform; true for all but the outermost tiles of any large box.
+    struct Tile { int id, T0, T1, T2; bool empty, interior; int c0; };
     struct Halo { int cnt, src, img, hz; bool edge, centre; };
     auto tile_of = [&](int slot) {
         Tile t;
@@ -487,6 +538,13 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
         }
         t.T0 = t0 * TXY; t.T1 = t1 * TXY; t.T2 = t2 * TZ;
         t.empty = t.T2 >= g.nc[2]; // (a slice beyond the grid: the parent tile was a clipped one)
+        // (the first and last cell of an open axis are edge cells: one cell further in)
+        const int m0 = b.pbc[0] ? 1 : 2, m1 = b.pbc[1] ? 1 : 2, m2 = b.pbc[2] ? 1 : 2;
+        // (orthogonal one-tile-per-workgroup instances only: the triclinic and the walked ones sit at their register limits, and the few
+        // scalars of this path cost them scratch memory)
+        t.interior = !TRI && !LOOP && !parent && t.T0 >= m0 && t.T0 + TXY + m0 <= g.nc[0] && t.T1 >= m1 && t.T1 + TXY + m1 <= g.nc[1] && t.T2 >= m2 &&
+                     t.T2 + TZ + m2 <= g.nc[2];
+        t.c0 = t.interior ? ((t.T0 - 1) * g.nc[1] + (t.T1 - 1)) * g.nc[2] + (t.T2 - 1) : 0;
         return t;
     };
     // halo cell of this thread: source range, image code, is it a centre cell
@@ -497,39 +555,49 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
             h.hz = tid - hcol * HZ;
             const int hx = (int)(((unsigned)hcol * ts.mhxy) >> 16), hy = hcol - hx * HXY;
             const int g0 = t.T0 + hx - 1, g1 = t.T1 + hy - 1, g2 = t.T2 + h.hz - 1;
-            // a cell beyond an OPEN face is the far side of the box in the reference's modulo walk (neighbor.cpp:18-27); with
-            // >= 4 cells on the axis its atoms are >= 2 rc from every centre of this tile: no hits, not staged
-            const bool in0 = b.pbc[0] ? (g0 >= -1 && g0 <= g.nc[0]) : (g0 >= 0 && g0 < g.nc[0]);
-            const bool in1 = b.pbc[1] ? (g1 >= -1 && g1 <= g.nc[1]) : (g1 >= 0 && g1 < g.nc[1]);
-            const bool in2 = b.pbc[2] ? (g2 >= -1 && g2 <= g.nc[2]) : (g2 >= 0 && g2 < g.nc[2]);
-            if (in0 && in1 && in2) {
-                bool over = false;
-                const int a0 = g0 < 0 ? g0 + g.nc[0] : (g0 >= g.nc[0] ? g0 - g.nc[0] : g0);
-                const int a1 = g1 < 0 ? g1 + g.nc[1] : (g1 >= g.nc[1] ? g1 - g.nc[1] : g1);
-                const int a2 = g2 < 0 ? g2 + g.nc[2] : (g2 >= g.nc[2] ? g2 - g.nc[2] : g2);
-                const int c = (a0 * g.nc[1] + a1) * g.nc[2] + a2; // (the host refuses grids of 2^31 cells or more)
+            bool in; // the cell is staged
+            int c;   // its number in the grid (the host refuses grids of 2^31 cells or more)
+            if (t.interior) { // every halo cell is a cell of the grid as it stands: no wrap, image code "no shift", no edge cell
+                in = true;
+                c = t.c0 + hx * (g.nc[1] * g.nc[2]) + hy * g.nc[2] + h.hz;
+                h.centre = hx >= 1 && hx <= TXY && hy >= 1 && hy <= TXY && h.hz >= 1 && h.hz <= TZ && g0 >= cen_lo && g0 < cen_hi;
+            } else {
+                // a cell beyond an OPEN face is the far side of the box in the reference's modulo walk (neighbor.cpp:18-27); with
+                // >= 4 cells on the axis its atoms are >= 2 rc from every centre of this tile: no hits, not staged
+                const bool in0 = b.pbc[0] ? (g0 >= -1 && g0 <= g.nc[0]) : (g0 >= 0 && g0 < g.nc[0]);
+                const bool in1 = b.pbc[1] ? (g1 >= -1 && g1 <= g.nc[1]) : (g1 >= 0 && g1 < g.nc[1]);
+                const bool in2 = b.pbc[2] ? (g2 >= -1 && g2 <= g.nc[2]) : (g2 >= 0 && g2 < g.nc[2]);
+                in = in0 && in1 && in2;
+                c = 0;
+                if (in) {
+                    const int a0 = g0 < 0 ? g0 + g.nc[0] : (g0 >= g.nc[0] ? g0 - g.nc[0] : g0);
+                    const int a1 = g1 < 0 ? g1 + g.nc[1] : (g1 >= g.nc[1] ? g1 - g.nc[1] : g1);
+                    const int a2 = g2 < 0 ? g2 + g.nc[2] : (g2 >= g.nc[2] ? g2 - g.nc[2] : g2);
+                    c = (a0 * g.nc[1] + a1) * g.nc[2] + a2;
+                    // image of the candidate cell seen from an in-grid centre cell: below the box -> raw coordinates are ~+L
+                    // away (n = +1); above -> n = -1
+                    const int n0 = g0 < 0 ? 1 : (g0 >= g.nc[0] ? -1 : 0);
+                    const int n1 = g1 < 0 ? 1 : (g1 >= g.nc[1] ? -1 : 0);
+                    const int n2 = g2 < 0 ? 1 : (g2 >= g.nc[2] ? -1 : 0);
+                    h.img = (n0 + 1) | ((n1 + 1) << 2) | ((n2 + 1) << 4);
+                    h.edge = (!b.pbc[0] && (a0 == 0 || a0 == g.nc[0] - 1)) || (!b.pbc[1] && (a1 == 0 || a1 == g.nc[1] - 1)) ||
+                             (!b.pbc[2] && (a2 == 0 || a2 == g.nc[2] - 1));
+                    // (cen_lo, cen_hi: the planes of axis 0 whose atoms want rows — all of them, or the planes of a decomposed system's own slab:
+                    // the ghost planes around it are staged as candidates, never scanned as centres)
+                    h.centre = hx >= 1 && hx <= TXY && hy >= 1 && hy <= TXY && h.hz >= 1 && h.hz <= TZ && g0 < g.nc[0] && g1 < g.nc[1] && g2 < g.nc[2] &&
+                               g0 >= cen_lo && g0 < cen_hi;
+                }
+            }
+            if (in) {
                 if (SLOT) { // the count, and the cell's first four ids at 4 c of the id list
                     const int n = cell_start[c];
                     h.src = c << 2;
                     h.cnt = min(n, SLOT_CAP);
-                    over = n > SLOT_CAP; // the rest of its atoms are on the spill list: the tile is listed
+                    if (n > SLOT_CAP) h.img |= 64; // the rest of its atoms are on the spill list: the tile is listed (bit 6: no part of the image code, combine_codes reads bits 0-5)
                 } else {
                     h.src = cell_start[c];
                     h.cnt = cell_start[c + 1] - h.src;
                 }
-                // image of the candidate cell seen from an in-grid centre cell: below the box -> raw coordinates are ~+L
-                // away (n = +1); above -> n = -1
-                const int n0 = g0 < 0 ? 1 : (g0 >= g.nc[0] ? -1 : 0);
-                const int n1 = g1 < 0 ? 1 : (g1 >= g.nc[1] ? -1 : 0);
-                const int n2 = g2 < 0 ? 1 : (g2 >= g.nc[2] ? -1 : 0);
-                h.img = (n0 + 1) | ((n1 + 1) << 2) | ((n2 + 1) << 4);
-                if (SLOT && over) h.img |= 64; // (bit 6: no part of the image code, combine_codes reads bits 0-5)
-                h.edge = (!b.pbc[0] && (a0 == 0 || a0 == g.nc[0] - 1)) || (!b.pbc[1] && (a1 == 0 || a1 == g.nc[1] - 1)) ||
-                         (!b.pbc[2] && (a2 == 0 || a2 == g.nc[2] - 1));
-                // (cen_lo, cen_hi: the planes of axis 0 whose atoms want rows — all of them, or the planes of a decomposed system's own slab:
-                // the ghost planes around it are staged as candidates, never scanned as centres)
-                h.centre = hx >= 1 && hx <= TXY && hy >= 1 && hy <= TXY && h.hz >= 1 && h.hz <= TZ && g0 < g.nc[0] && g1 < g.nc[1] && g2 < g.nc[2] &&
-                           g0 >= cen_lo && g0 < cen_hi;
             }
         }
         return h;
@@ -592,7 +660,9 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
         // ---- stage this cell's atoms
         if (ok && cnt > 0) {
             double X0, Y0, Z0, XS, YS, ZS;
-            const int code0 = combine_codes(img, img::ATOM_NEUTRAL); // an atom inside the box (image number 0): the cell's own shift
+            // an atom inside the box (image number 0): the cell's own shift — none in an interior tile, known at the branch
+            const bool plain = !TRI && tile.interior;
+            const int code0 = plain ? NEUTRAL3 : combine_codes(img, img::ATOM_NEUTRAL);
             if (TRI) { // corner of the tile's halo and the cell's lattice shift, through the cell vectors (rows of h)
                 // (cell k of axis d starts at the fraction k * rc / thickness_d: cells of perpendicular width rc, grid.hpp)
                 const double f0 = (double)(T0 - 1) * (cw / b.thick[0]) + (double)img::axis(code0, 0);
@@ -604,8 +674,12 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                 X0 = XS; Y0 = YS; Z0 = ZS;
             } else {
                 X0 = b.o[0] + (double)(T0 - 1) * cw; Y0 = b.o[1] + (double)(T1 - 1) * cw; Z0 = b.o[2] + (double)(T2 - 1) * cw;
-                XS = X0 + b.h[0] * (double)img::axis(code0, 0); YS = Y0 + b.h[4] * (double)img::axis(code0, 1);
-                ZS = Z0 + b.h[8] * (double)img::axis(code0, 2);
+                if (plain) { // (X0 + L * 0: the same number)
+                    XS = X0; YS = Y0; ZS = Z0;
+                } else {
+                    XS = X0 + b.h[0] * (double)img::axis(code0, 0); YS = Y0 + b.h[4] * (double)img::axis(code0, 1);
+                    ZS = Z0 + b.h[8] * (double)img::axis(code0, 2);
+                }
             }
             const float flo = (float)(-1.5 * cw);
             const float fhx = (float)(((double)HXY + 1.5) * cw), fhz = (float)(((double)HZ + 1.5) * cw);
@@ -713,6 +787,13 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
             const int r3 = (r * 11) >> 5;
             return cbv + __mul24(r3, A2 - 3 * HZ) + __mul24(r, HZ) - (A2 + HZ);
         };
+        // the same from the shape's byte table (one-byte instance): cbk = centre's cell + ts.ro_bias, sel = the run's number 0 ... 7, or
+        // RUN8_SEL for run 8 (run_offset_table) — one v_perm_b32 and an addition where the arithmetic above is two multiplications
+        // (the triclinic instances keep the arithmetic: three more launch words in scalar registers cost them scratch memory)
+        constexpr unsigned R8 = TRI ? 8u : RUN8_SEL;
+        auto run_at = [&](int cbv, unsigned cbk, unsigned sel) {
+            return TRI ? run_cell(cbv, (int)sel) : (int)(cbk + __builtin_amdgcn_perm(ts.ro_hi, ts.ro_lo, sel));
+        };
         // Centres go out in chunks of rw (a full wave of them); chunk c is taken by wave (c + jt) mod 4 — a tile of 150 centres
         // keeps three waves busy with full registers and leaves the fourth free, and the rotation spreads the free one over the
         // CU's four SIMDs from tile to tile (an even split, 38 lanes in each of four waves, costs four chunk passes for three)
@@ -744,15 +825,17 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                     for (int r = 0; r < 9; ++r) {
                         const int len = (int)(hv[r] >> 16);
                         scan_run12_asm(f4_lds + ((hv[r] & 0xffffu) << 4), s.x, s.y, s.z, negc, mk[r], w);
-                        mk[r] = (mk[r] << 20) & (~0u << ((32 - len) & 31)) & (len > 0 ? ~0u : 0u); // slots past the end of the run
+                        mk[r] = keep_top(mk[r] << 20, len); // slots past the end of the run (len <= 12; an empty run keeps nothing)
                     }
                 } else {
 #pragma unroll
                     for (int r = 0; r < 9; ++r) {
                         const int len = (int)(hv[r] >> 16), la = WIDE ? min(len, 32) : len;
                         scan_run_asm(f4_lds + ((hv[r] & 0xffffu) << 4), la, s.x, s.y, s.z, negc, mk[r], w);
-                        mk[r] &= ~0u << (run_slots(la) - la); // slots past the end of the run
-                        if (TK8) mk[r] <<= (32 - run_slots(la)) & 31; // (an empty run: mask 0, shift 0)
+                        if (TK8) // top-aligned, slots past the end of the run cleared: the top la bits as keep_top(m, la - 1) of all but the first
+                            // (la = 32 keeps the whole mask; an empty run: mask 0 from the scan, shift 0, all of nothing kept)
+                            mk[r] = and_not(mk[r] << ((32 - run_slots(la)) & 31), 0x7fffffffu >> ((la - 1) & 31));
+                        else mk[r] &= ~0u << (run_slots(la) - la); // slots past the end of the run
                         if (WIDE) {
                             const int lb = min(len - la, 32), lc = len - la - lb;
                             mk2[r] = 0;
@@ -852,10 +935,14 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                         kept8 = max(0, min(n8, kept - (hits - n8)));
                     }
                     if (FCNA) { // atoms without 12 or 14 neighbours keep the caller's value (cna.cpp:456)
+                        const unsigned cbk = (unsigned)cb + ts.ro_bias;
                         auto index_of = [&](int a) {
                             const unsigned t = my[a];
-                            const int r = (TK8 && a >= kept - kept8) ? 8 : (int)(t >> JB);
-                            return (int)(hr[run_cell(cb, r)] & 0xffffu) + (int)(t & ((1u << JB) - 1u));
+                            if (TK8) {
+                                const unsigned sel = a >= kept - kept8 ? R8 : t >> JB;
+                                return (int)(hr[run_at(cb, cbk, sel)] & 0xffffu) + (int)(t & ((1u << JB) - 1u));
+                            }
+                            return (int)(hr[run_cell(cb, (int)(t >> JB))] & 0xffffu) + (int)(t & ((1u << JB) - 1u));
                         };
                         int label = 0;
                         if (hits == 12 && M >= 12) label = lane_fcna_f32<12>(index_of, f4, negc, W);
@@ -878,6 +965,7 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1) maxk = max(maxk, __shfl_xor(maxk, d, 64));
                 const unsigned *myw = reinterpret_cast<const unsigned *>(my);
+                const unsigned cbk = (unsigned)cb + ts.ro_bias; // (run_at)
                 unsigned tw[4];
 #pragma unroll
                 for (int v = 0; v < 4; ++v) tw[v] = (4 * v < M) ? myw[v] : 0u;
@@ -900,9 +988,9 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                             const int sx = g0 + u;
                             h[u] = sx < kept;
                             const unsigned t = (tw[sx >> 2] >> (8 * (sx & 3))) & 255u;
-                            int r = (sx >= kept - kept8) ? 8 : (int)(t >> 5);
-                            r = h[u] ? r : 4; // a lane whose row is shorter: the first atom of its own run, result unused
-                            k[u] = (int)(hr[run_cell(cb, r)] & 0xffffu) + (h[u] ? (int)(t & 31u) : 0);
+                            unsigned r = (sx >= kept - kept8) ? R8 : t >> 5;
+                            r = h[u] ? r : 4u; // a lane whose row is shorter: the first atom of its own run, result unused
+                            k[u] = (int)(hr[run_at(cb, cbk, r)] & 0xffffu) + (h[u] ? (int)(t & 31u) : 0);
                         }
                         double2 cj[4];
                         double zj[4], d2[4];
@@ -914,15 +1002,14 @@ __global__ __launch_bounds__(NW * 64, (TK8 && (!FCNA || !LOOP)) ? 16 / NW : 1) v
                             nid[u] = __float_as_int(f4[k[u]].w);
                             sh[u] = (!TRI && general_tile) ? (int)lsh[k[u]] : 0;
                         }
-                        bool slow = false;
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             if (TRI) d2[u] = exact_d2<2>(b, cj[u].x, cj[u].y, zj[u], xi, yi, zi, 0);
                             else if (general_tile) d2[u] = exact_d2<1>(b, cj[u].x, cj[u].y, zj[u], xi, yi, zi, sh[u]);
                             else d2[u] = exact_d2<0>(b, cj[u].x, cj[u].y, zj[u], xi, yi, zi, 0);
                             d2[u] = h[u] ? d2[u] : 1.0;
-                            slow = slow || !sqrt_fast_ok(d2[u]);
                         }
+                        const bool slow = !sqrt_fast_ok4(d2);
                         double rr[4]; // neighbor.cpp:174 — the four roots as one straight-line block: their dependent chains interleave
                         if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow) == 0, 1)) {
 #pragma unroll
@@ -1510,6 +1597,13 @@ extern "C" int mdh_debug_neighbor_plan(int *plan8)
     for (int k = 0; k < 8; ++k) plan8[k] = mdh::lane::g_last_plan[k];
     if (plan8[0] > 0 && mdh::last_grid_was_slot()) plan8[4] |= 256; // bit 8 of [4]: the last neighbor build's cell grid was a slot grid (CellGrid::slot_cap)
     mdh::lane::g_last_plan[7] = 0; // [7] = 1: the plan was made since the last query
+    return MDH_OK;
+}
+extern "C" int mdh_debug_run_offset_table(int txy, int tz, unsigned *out3)
+{
+    if (txy < 1 || tz < 1 || (int64_t)(txy + 2) * (txy + 2) * (tz + 2) > mdh::lane::RUN_TABLE_HALO) return MDH_ERR_ARG;
+    const mdh::lane::Shape s = mdh::lane::make_shape(txy, tz, 1, 1);
+    out3[0] = s.ro_lo; out3[1] = s.ro_hi; out3[2] = s.ro_bias;
     return MDH_OK;
 }
 

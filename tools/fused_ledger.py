@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Instruction ledger of the fused label in the headline instance of the tile kernel, k_neighbor_lane<0,0,0,1,1,1> (FCNA=1, TK8=1,
-IND=1): the gfx950 ISA of mdapy_amd/csrc/neighbor_lane.hip with line tables, the label's instructions attributed to three phases
+"""Instruction ledger of the fused label in the headline instance of the tile kernel, k_neighbor_lane<0,0,0,1,1,1,1> (FCNA=1, TK8=1,
+IND=1, SLOT=1): the gfx950 ISA of mdapy_amd/csrc/neighbor_lane.hip with line tables, the label's instructions attributed to three phases
 by the source line they came from — index and LDS reads (lane_fcna_f32 up to the pair tests, the ticket decode of the FCNA block),
 pair tests (pair_tests_f32*), signatures (everything else of cna_core.hpp that the label inlines: the certificate, the pair-count or
 word-loop signatures) — and weighted by issue class (profiles/r02_ubench_valu_rate3.txt, docs/NOTEBOOK.md "Micro-benchmarks"):
@@ -13,7 +13,7 @@ by name; the sum of a certified wave's hot path leaves out the general signature
     python tools/fused_ledger.py [REPO_ROOT]      (default: this repository; any checkout of it, e.g. the parent commit, works)"""
 import collections, os, re, shutil, subprocess, sys, tempfile
 
-KERNEL = "_ZN3mdh4lane15k_neighbor_laneILb0ELb0ELb0ELb1ELb1ELb1E"
+KERNEL = "_ZN3mdh4lane15k_neighbor_laneILb0ELb0ELb0ELb1ELb1ELb1ELb1EE"
 SGPR_RE = re.compile(r"(?<![a-z_])(s\d+|s\[\d+:\d+\]|vcc|vcc_lo|vcc_hi|exec|exec_lo|m0)(?![a-z_0-9])")
 TRANS = ("v_rcp", "v_rsq", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")
 
@@ -121,7 +121,7 @@ def main():
         args = s[len(op):]
         n[ph] += 1
         cyc[ph] += cost(op, args)
-    print(f"fused label of {KERNEL}<0,0,0,1,1,1> ({root}): static VALU instructions of the 12-hit path")
+    print(f"fused label of {KERNEL} ({root}): static VALU instructions of the 12-hit path")
     print(f"{'phase':34s} {'instr':>6s} {'cycles (weighted)':>18s}")
     for ph in ("index + LDS reads", "pair tests", "certificate", "signatures"):
         if n[ph]:
