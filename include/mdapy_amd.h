@@ -509,6 +509,32 @@ int mdh_eam(const double *x, const double *y, const double *z, const int *type, 
             const double *rho_knots, const double *rphi_knots, int nelem, int nrho, double drho, int nr, double dr, double rc,
             int accumulate, double *energy, double *force, double *virial, int64_t n_real, double *virial_sum9, int space, void *stream);
 
+/* ---- _nepcal ---- */
+/* replaces _nepcal.NEPCalculator.calculate / get_descriptors / get_latentspace        src/neppy.cpp:170-288
+ * Neuroevolution-potential energies (N) f64, forces (N x 3), virials (N x 9, row-major, the reference's sign: virial_i =
+ * sum_j r_ij (x) f_ji), descriptors (N x dim, times the scalers) and latent space (N x neurons, w1[n] tanh(..)) over a cutoff list
+ * (verlet, dist N x M; nn N) that reaches the model's largest cutoff; entries beyond a pair's cutoff are skipped.  Every output may
+ * be NULL and is WRITTEN, never added to.  virial_sum9 (9 f64; needs virial): the column sums of the first n_real rows of virial,
+ * in the fixed two-level order of mdh_eam.  All sums run in an order that depends on the list alone, no atomics: the same bits on
+ * every run.  The force on i gathers f_ij - f_ji over its row; f_ji is looked up where row j names i, so the list must be
+ * symmetric (a cutoff list is).
+ * type (N, i32) holds places in the model FILE's element list; type_map_host (nfile i32, host) takes them to the model's own types
+ * 0 .. T-1, or -1: such an atom contributes nothing and receives zeros.
+ * The model: head12_host (host i32: T, n_max_radial+1, basis_size_radial+1, n_max_angular+1, basis_size_angular+1, l_max 3-body,
+ * 4-body, 5-body, neurons, ZBL mode 0 none / 1 universal / 2 typewise outer radius, length of the block, 0), zbl3_host (host f64:
+ * inner, outer, typewise factor) and the f64 block `model` in the arrays' memory space, in this order: radial cutoff per type (T),
+ * angular cutoff per type (T), atomic number per type (T), covalent radius per type (T), descriptor scalers (dim), radial
+ * coefficients c[t1][t2][n][k], angular coefficients c[t1][t2][n][k], per type the network w0 (neurons x dim), b0 (neurons),
+ * w1 (neurons) and the type's bias (nep5; 0.0 otherwise), then the common bias.  dim = (n_max_radial+1) + (n_max_angular+1) *
+ * (l_max_3body + [4-body] + [5-body]).
+ * MDH_ERR_ARG before any launch: l_max out of scope (3-body 1..4, 4-body 0 or 2, 5-body 0 or 1), a model above the compiled maxima
+ * (96 file types, n_max 15, basis_size 16, 128 neurons), a block whose length does not follow from the header, a type map entry
+ * outside [-1, T), with host arrays a type outside [0, nfile), M >= 2^23, n_real outside [0, N], virial_sum9 without virial. */
+int mdh_nep(const double *x, const double *y, const double *z, const int *type, int64_t N, const int *type_map_host, int nfile,
+            const double *box9, const double *origin3, const int *boundary3, const int *verlet, const double *dist, const int *nn, int64_t M,
+            const double *model, const int *head12_host, const double *zbl3_host, int64_t n_real, double *energy, double *force, double *virial,
+            double *virial_sum9, double *descriptor, double *latent, int space, void *stream);
+
 /* ---- _fire ------------------------------------------------------------ */
 /* The arithmetic of the FIRE minimizer (src/mdapy/minimizer.py:270-375 does it in numpy) on (n, 3) row-major f64 arrays; no
  * reference counterpart in C++.  f64, no contraction.  The scalars the steps hand to one another live in a RECORD of

@@ -18,6 +18,7 @@ from .warren_cowley_parameter import WarrenCowleyParameter
 from .atomic_strain import AtomicStrain
 from .calculator import CalculatorMP
 from .eam import EAM
+from .nep import NEP
 from . import minimizer
 from .minimizer import FIRE
 from .chill_plus import ChillPlus
@@ -35,7 +36,7 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "CalculatorMP", "EAM", "FIRE", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
+    "AtomicStrain", "CalculatorMP", "EAM", "NEP", "FIRE", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
     "Trajectory", "unwrap_trajectory", "VDW_RADII", "vdw_radius",
     "build_crystal", "CreatePolycrystal", "get_num_threads",
 ]

@@ -283,6 +283,10 @@ __device__ __forceinline__ void raise_max(int *out, int m)
 // GPU.  The reference reads out of bounds there (undefined behaviour), so any defined result is as good as its.
 __device__ __forceinline__ int safe_id(int j, int64_t fallback, int64_t n) { return (unsigned)j < (unsigned)n ? j : (int)fallback; }
 
+// sum9[c] = the sum of column c of the first n_real rows of an (n x 9) virial array, in a fixed two-level order without atomics
+// (eam.hip): what every calculator's stress is made of
+void launch_virial_sum(Scope &sc, const double *virial, int64_t n_real, double *sum9);
+
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
 // Every translation unit of the library is one code object, loaded by the HIP runtime at the first launch of one of its

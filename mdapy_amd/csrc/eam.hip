@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void k_column_sums9(const double *__restrict__
     }
 }
 
-static void launch_virial_sum(Scope &sc, const double *virial, int64_t n_real, double *sum9)
+void launch_virial_sum(Scope &sc, const double *virial, int64_t n_real, double *sum9)
 {
     const int blocks = (int)std::min<int64_t>(VSUM_BLOCKS, std::max<int64_t>(1, (n_real * 9 + VSUM_THREADS - 1) / VSUM_THREADS));
     double *partial = sc.alloc_n<double>((size_t)blocks * 9);

@@ -29,6 +29,8 @@ from . import _fccpft as fccpft
 from . import _lindemann as lindemann
 # (not in NAMES either: neither the reference nor the oracle has a compiled MSD; its tests install a restatement as kernels.msd)
 from . import _msd as msd
+# (not in NAMES either: the oracle has no NEP; its tests install a restatement as kernels.nep)
+from . import _nep as nep
 from . import _neighbor as neighbor
 from . import _order as order
 from . import _polycrystal as polycrystal
