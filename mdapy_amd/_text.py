@@ -4,6 +4,7 @@ Two pieces: :func:`stream_to_device` moves a file's bytes into HBM through two p
 the file while the previous one crosses PCIe), :func:`parse_table` runs ``mdh_parse_table`` on the resident text and
 patches the few fields the device hands back (``float()`` / ``int()`` on the host — the reference's own conversion)."""
 import ctypes
+import re
 
 import numpy as np
 
@@ -96,25 +97,43 @@ def parse_table(text, nrows, kinds, redo_cap=1 << 16):
         where = todo[:, 0].astype(np.int64)
         off = (todo[:, 1] >> 16).astype(np.int64)
         ln = (todo[:, 1] & 0xFFFF).astype(np.int64)
-        span = np.where(ln == 0xFFFF, 4096, ln)  # longer than the length field: up to the next blank, found on the host
+        span = np.where(ln == 0xFFFF, 0, ln)  # (0xFFFF: that long or longer — those are fetched one by one, below)
         starts = np.concatenate([[0], np.cumsum(span)])[:-1]
         idx = (np.repeat(off - starts, span) + np.arange(int(span.sum()))).clip(max=max(nbytes - 1, 0))
         blob = text[t.from_numpy(idx).to(text.device)].cpu().numpy().tobytes()
         rows_of, vals_of = {}, {}
         for q in range(nredo):
             r, c = divmod(int(where[q]), ncol)
-            raw = blob[int(starts[q]): int(starts[q] + span[q])]
-            tok = (raw.split()[0] if ln[q] == 0xFFFF else raw).decode()
+            raw = _long_token(text, int(off[q]), nbytes) if ln[q] == 0xFFFF else blob[int(starts[q]): int(starts[q] + span[q])]
+            tok = raw.decode()
             if kinds[c] == STR:
                 long_strings.setdefault(c, {})[r] = tok
             else:  # float() / int() raise ValueError for what they reject, as the reference's conversion does
+                val = float(tok) if kinds[c] == FLOAT else int(tok)
+                if kinds[c] == INT and not -2 ** 31 <= val < 2 ** 31:
+                    raise OverflowError(f"Python integer {val} out of bounds for int32")
                 rows_of.setdefault(c, []).append(r)
-                vals_of.setdefault(c, []).append(float(tok) if kinds[c] == FLOAT else int(tok))
+                vals_of.setdefault(c, []).append(val)
         for c, rows in rows_of.items():
             dev = cols[c].dev()
             dev[t.as_tensor(rows, dtype=t.int64, device=dev.device)] = t.as_tensor(vals_of[c], dtype=dev.dtype, device=dev.device)
     out = [_unpack_strings(col, long_strings.get(c)) if k == STR else col for c, (k, col) in enumerate(zip(kinds, cols))]
     return out, lines
+
+
+_TOKEN_END = re.compile(rb"[ \t\r\n]")  # the kernel's blanks and the end of the row
+
+
+def _long_token(text, off, nbytes):
+    """the token that starts at byte ``off`` and is too long for the hand-back list's 16-bit length: all of it, up to the
+    next blank, the end of the row or the end of the text, read in growing pieces"""
+    got, want = b"", 1 << 17
+    while True:
+        got += text[off + len(got): min(off + want, nbytes)].cpu().numpy().tobytes()
+        end = _TOKEN_END.search(got)
+        if end or off + len(got) >= nbytes:
+            return got[: end.start()] if end else got
+        want *= 2
 
 
 def _unpack_strings(packed, long_ones=None):

@@ -37,16 +37,34 @@ def _open(path, mode="rb"):
 # ---------------------------------------------------------------------------------------------------------------------
 # the atom table
 # ---------------------------------------------------------------------------------------------------------------------
+def _int32(values: np.ndarray) -> np.ndarray:
+    """int64 -> int32, refusing what does not fit (numpy's own refusal when the reference converts such a field)"""
+    out = values.astype(np.int32)
+    if not np.array_equal(out, values):
+        raise OverflowError(f"Python integer {int(values[out != values][0])} out of bounds for int32")
+    return out
+
+
 def _table_on_host(body: bytes, nrows: int, names: List[str], kinds: List[int], source: str) -> Dict[str, np.ndarray]:
-    """host tokenizer: pandas' C reader with exact (round-trip) conversion when it accepts the table, str.split otherwise"""
+    """host tokenizer: pandas' C reader with exact (round-trip) conversion where the table is plain, str.split otherwise.
+    The table is the next ``nrows`` lines, as in the reference (load_save.py:141-175): a blank line is a row without fields, not
+    something to skip; a row that lacks its last fields is an error even where those are strings; an integer column holds
+    integers (``3.0`` and ``1e3`` are errors) that fit int32.  pandas would let each of these pass (it skips, fills in ``''``,
+    reads ``3.0`` as 3 and wraps 2^31), so it only gets the tables it reads as they are: the integer columns are left to its
+    type inference, and anything but int64 there — like every other doubt — sends the table to str.split, whose conversions are
+    the reference's."""
     try:
         import pandas as pd
 
-        dtypes = {n: {FLOAT: np.float64, INT: np.int32, STR: str}[k] for n, k in zip(names, kinds)}
+        dtypes = {n: {FLOAT: np.float64, STR: str}[k] for n, k in zip(names, kinds) if k != INT}
         df = pd.read_csv(io.BytesIO(body), sep=r"\s+", header=None, names=list(names), nrows=nrows, dtype=dtypes, engine="c",
-                         float_precision="round_trip", na_filter=False, index_col=False, usecols=range(len(names)))
-        if len(df) == nrows and df.shape[1] == len(names):
-            return {n: (df[n].to_numpy(dtype=object) if k == STR else np.ascontiguousarray(df[n].to_numpy())) for n, k in zip(names, kinds)}
+                         float_precision="round_trip", na_filter=False, index_col=False, usecols=range(len(names)), skip_blank_lines=False)
+        plain = len(df) == nrows and df.shape[1] == len(names) and all(df[n].dtype == np.int64 for n, k in zip(names, kinds) if k == INT)
+        if plain and kinds[-1] == STR and (df[names[-1]] == "").any():  # (a missing number fails to convert; a missing string comes back empty)
+            plain = False
+        if plain:
+            return {n: (df[n].to_numpy(dtype=object) if k == STR else _int32(df[n].to_numpy()) if k == INT else np.ascontiguousarray(df[n].to_numpy()))
+                    for n, k in zip(names, kinds)}
     except Exception:
         pass
     rows = [ln.split()[: len(names)] for ln in body.decode().splitlines()[:nrows]]
@@ -55,8 +73,7 @@ def _table_on_host(body: bytes, nrows: int, names: List[str], kinds: List[int], 
     out = {}
     for j, (n, k) in enumerate(zip(names, kinds)):
         col = [r[j] for r in rows]
-        out[n] = np.array(col, dtype=object) if k == STR else np.array(col, dtype=np.float64 if k == FLOAT else np.int64).astype(
-            np.float64 if k == FLOAT else np.int32)
+        out[n] = np.array(col, dtype=object) if k == STR else np.array(col, dtype=np.float64) if k == FLOAT else _int32(np.array(col, dtype=np.int64))
     return out
 
 

@@ -11,30 +11,10 @@ import pytest
 
 import mdapy_amd as mp
 import mdapy_amd.load_save as LS
+from _readers import both as _both, same as _same
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _both(path, monkeypatch):
-    with monkeypatch.context() as m:
-        m.setattr(LS, "DEVICE_MIN_BYTES", 0)
-        dev = LS.read_file(path)
-    with monkeypatch.context() as m:
-        m.setattr(LS, "have_gpu", lambda: False)
-        host = LS.read_file(path)
-    return dev, host
-
-
-def _same(dev, host):
-    assert dev[0].columns == host[0].columns and dev[2] == host[2]
-    assert np.array_equal(dev[1].box, host[1].box) and np.array_equal(dev[1].origin, host[1].origin)
-    for c in dev[0].columns:
-        a, b = dev[0][c].to_numpy(), host[0][c].to_numpy()
-        if a.dtype == object or b.dtype == object:
-            assert list(a) == list(b), c
-        else:
-            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), c
 
 
 def test_sample_files_device_equals_host(monkeypatch):

@@ -127,3 +127,23 @@ def test_build_system_facade(tmp_path):
         BuildSystem.from_file("frame.cfg")
     with pytest.raises(ValueError, match="outside its input side"):
         BuildSystem.from_file("POSCAR.poscar")
+
+
+def test_host_tokenizer_takes_the_next_n_lines_as_the_table(tmp_path, monkeypatch):
+    """the reference's table is the n lines after the header (load_save.py:141): a blank or whitespace-only line among them is a
+    row without fields and a row without its last (string) field is too short — errors, not rows to skip or to fill in; blank
+    lines after the table are nobody's business"""
+    monkeypatch.setattr(LS, "have_gpu", lambda: False)
+    rows = DUMP_ORTHO.split("\n")
+    for bad in (rows[:10] + [""] + rows[10:], rows[:10] + [" \t "] + rows[10:], rows[:9] + [""] + rows[9:], rows[:10] + ["2 2 3 4 5 0.25"] + rows[11:]):
+        with pytest.raises(ValueError, match="expected 3 atom rows"):
+            LS.read_file(_write(tmp_path, "bad.dump", "\n".join(bad)))
+    for spelling, error in (("3.0", ValueError), ("1e3", ValueError), ("12a", ValueError), ("2147483648", OverflowError), ("-2147483649", OverflowError),
+                            ("4294967297", OverflowError)):  # an integer column holds integers that fit int32 (load_save.py:167-169)
+        with pytest.raises(error):
+            LS.read_file(_write(tmp_path, "id.dump", DUMP_ORTHO.replace("\n3 1 6", f"\n{spelling} 1 6")))
+    fr, _, _ = LS.read_file(_write(tmp_path, "id.dump", DUMP_ORTHO.replace("\n3 1 6", "\n+2147483647 -0 6").replace("\n1 1 0.5", "\n-2147483648 0007 0.5")))
+    assert list(fr["id"].to_numpy()) == [-2 ** 31, 2, 2 ** 31 - 1] and list(fr["type"].to_numpy()) == [7, 2, 0] and fr["id"].dtype == np.int32
+    for tail in ("\n\n\n", "   \n", "\r\n \r\n"):
+        fr, _, _ = LS.read_file(_write(tmp_path, "tail.dump", DUMP_ORTHO + tail))
+        assert list(fr["id"].to_numpy()) == [1, 2, 3] and list(fr["element"].to_numpy()) == ["Cu", "Zr", "Cu"]

@@ -2,11 +2,9 @@
 for the host as well) against Python's float() — which is what the reference's readers return for every field
 (src/mdapy/load_save.py:159-175) — and the generated table of powers of five against exact integer arithmetic."""
 import ctypes
-import random
 import struct
 
-import numpy as np
-
+import _text_cases as C
 from mdapy_amd import _lib
 
 
@@ -44,30 +42,13 @@ def test_power_of_five_table_is_exact():
         assert (int(out[0]) << 64) | int(out[1]) == c, q
 
 
+def _by_class(*tags):
+    return [s for tag, s in C.cases() if tag in tags]
+
+
 def test_fields_round_exactly_like_float():
-    rng = random.Random(5)
-    cases = ["0", "-0", "0.0", "1", "-1.5", "3.615", "1e22", "1e23", "9007199254740993", "9007199254740992.5", "0.1", "1e-5",
-             "123456789012345678", "1234567890123456789", "4.9e-324", "2.4703282292062327e-324", "2.4703282292062328e-324",
-             "1.7976931348623157e308", "1.7976931348623159e308", "1e309", "1e-400", "2.2250738585072011e-308", "2.2250738585072014e-308",
-             "+7.25", ".5", "5.", "1E5", "1e+5", "00012.500", "8.5e0", "0.000001", "123456.789e-3", "1.0000000000000002"]
-    for _ in range(60000):
-        kind = rng.randrange(6)
-        if kind == 0:  # shortest round-trip spelling of a random double
-            v = struct.unpack("<d", struct.pack("<Q", rng.getrandbits(64)))[0]
-            if v != v or v in (float("inf"), float("-inf")):
-                continue
-            cases.append(repr(v))
-        elif kind == 1:
-            cases.append("%.6g" % rng.uniform(-500, 500))
-        elif kind == 2:
-            cases.append("%.15f" % rng.uniform(-500, 500))
-        elif kind == 3:
-            cases.append("%de%d" % (rng.randrange(10 ** 19), rng.randrange(-340, 300)))
-        elif kind == 4:  # exactly halfway between two doubles, and its neighbours
-            m = rng.randrange(1 << 52, 1 << 53)
-            cases.append(str(2 * m + 1) + rng.choice(["", "e-1", "e0"]))
-        else:
-            cases.append("%.17e" % rng.lognormvariate(0, 40))
+    cases = _by_class("basic", "repr", "g6", "f15", "int19", "half53", "e17")
+    assert len(cases) > 59000
     redo = 0
     for s in cases:
         rc, v = _conv(s)
@@ -80,11 +61,10 @@ def test_fields_round_exactly_like_float():
 
 
 def test_long_fields_are_decided_or_handed_back():
-    rng = random.Random(9)
+    cases = _by_class("long")
+    assert len(cases) == 20000
     decided = 0
-    for _ in range(20000):
-        digits = "".join(rng.choice("0123456789") for _ in range(rng.randrange(20, 40)))
-        s = digits[:3] + "." + digits[3:] + rng.choice(["", "e-7", "e12"])
+    for s in cases:
         rc, v = _conv(s)
         assert rc in (0, 1)
         if rc == 0:
@@ -95,5 +75,54 @@ def test_long_fields_are_decided_or_handed_back():
     for s in ("9007199254740993.000000000000000001", "9007199254740993.0000000000000000000"):  # just above / exactly on a halfway point
         rc, v = _conv(s)
         assert rc == 1 or _same(v, float(s))
-    for s, want in (("nan", 1), ("inf", 1), ("-inf", 1), ("abc", 2), ("1.5x", 1), ("1.5y", 2), ("", 2), ("1e", 2), ("0x10", 1), ("--1", 2)):
+    for s, want in C.LISTED:
         assert _conv(s)[0] == want, s
+    for s in C.MORE_NON_NUMBERS:
+        assert _conv(s)[0] == {"naninf": 1, "hex": 1, "bad": 2}[C.kind_of(s)], s
+
+
+def test_halfway_subnormal_zero_padded_and_swept_fields():
+    """the classes of _text_cases.py that reach what plain coordinates never do: exact halfway points with decimal exponents
+    -4 .. 23 (the round-to-even branch) and their neighbours one unit of the 19th digit away, the subnormal band, zeros that
+    are not significant digits, eight significands against every decimal exponent from underflow to overflow, and spellings of
+    sign and exponent.  Bit for bit float() (the sign of -0.0 included); a field is handed back only when it has more than
+    19 significant digits and the first 19 leave the rounding open."""
+    per_class = {}
+    exps = set()
+    for tag, s in C.cases():
+        if tag not in C.NEW_CLASSES:
+            continue
+        per_class[tag] = per_class.get(tag, 0) + 1
+        rc, v = _conv(s)
+        if C.significant_digits(s) <= 19:
+            assert rc == 0, (tag, s)
+        else:
+            assert rc == (0 if C.decided_with_19_digits(s) else 1), (tag, s)
+        if rc == 0:
+            assert _same(v, float(s)), (tag, s, v, float(s))
+        if tag == "halfway" and "e" in s:
+            exps.add(int(s.split("e")[1]))
+    assert set(per_class) == set(C.NEW_CLASSES) and per_class["halfway"] > 500 and per_class["sweep"] == 8 * 657
+    assert exps >= set(range(-4, 24))  # the decimal exponents at which a 19-digit significand can lie exactly halfway
+    for s, want in (("-0", -0.0), ("-0.0", -0.0), ("+.5", 0.5), ("5.", 5.0), ("1E5", 1e5), ("1e+05", 1e5), ("1e00000000000000000005", 1e5),
+                    ("1e-99999999", 0.0)):
+        rc, v = _conv(s)
+        assert rc == 0 and _same(v, want), s
+
+
+def test_every_case_of_the_shared_list_agrees_with_float():
+    """the whole list, as the GPU test feeds it to the kernels: 0 mismatches, nothing of <= 19 significant digits handed back"""
+    mismatches, handed_back_short = [], []
+    for tag, s in C.cases():
+        rc, v = _conv(s)
+        kind = C.kind_of(s)
+        if kind != "number":
+            assert rc == (2 if kind == "bad" else 1), s
+            continue
+        if rc == 0 and not _same(v, float(s)):
+            mismatches.append(s)
+        if rc != 0 and C.significant_digits(s) <= 19:
+            handed_back_short.append(s)
+        assert rc == (0 if C.decided_with_19_digits(s) else 1), s
+    assert not mismatches, (len(mismatches), mismatches[:20])
+    assert not handed_back_short, handed_back_short[:20]
