@@ -672,6 +672,41 @@ int mdh_lindemann_global(const double *pos, int64_t F, int64_t N, double *pair_s
 int mdh_lindemann_all(const double *pos, int64_t F, int64_t N, double *pair_mean, double *pair_var, double *lindemann_frame,
                       double *lindemann_atom, int segments, int space, void *stream);
 
+/* ---- _sqs -------------------------------------------------------------- */
+/* Special quasirandom structures: cluster correlations of a lattice alloy, and a Monte-Carlo search over R independent chains
+ * (replaces _sqs.SQSEngine's correlations / per_channel_delta / objective / run_mc, src/sqs.cpp:246-509).  The header comment of
+ * csrc/sqs.hip pins the formulation (integer histograms of species multisets per (body, shell) group), the order of every
+ * floating-point operation, and the library's own counter-based random numbers; mdapy_amd/_sqs.py builds the tables.
+ *
+ * The model, all in HOST memory (space must be MDH_HOST; every index is checked before a kernel reads it):
+ *   dims_host (8) i64   N atoms, m species, I instances, G groups, C channels, H histogram bins, entries of tab, entries of a2i
+ *   inst_atoms (I, 4) i32 (unused slots -1), inst_group (I) i32
+ *   a2i_off (N + 1) i32, a2i: the instances that hold an atom, each once
+ *   group_i (G, 6) i32  n_pts, first bin, first channel, channels, instances, K = C(m + n_pts - 1, n_pts)
+ *   chan_i (C, 3) i32   group, n_pts - 2, offset of its K numbers in tab
+ *   chan_d (C, 4) f64   target, diameter, weight in mode 0, weight in mode 1
+ *   tab f64             symmetrised basis products per (channel, multiset)
+ *   msidx i32           multiset index of an ordered species tuple read as a base-m number; sections of m^2, m^3, m^4 entries
+ *   objp (10) f64       mode (0 abs, 1 atat), atat_tol, d_min, bodies, maxdist0[3], reward[3]
+ * Limits, MDH_ERR_ARG beyond them and before any device work: 2 <= N <= 4096, 2 <= m <= 8, bodies 2..4, G <= 1024,
+ * 16 C + 4 H + 4 ceil(G / 32) + 2 (N rounded up to 8) <= 65536 (one replica's state in LDS), 1 <= R <= 2^20, T > 0.
+ *
+ * count: types (R, N) i32 in [0, m).  hist (R, H) i32, corr (R, C), delta (R, C) = |corr - target|, objective (R): each may be
+ * NULL (not wanted). */
+int mdh_sqs_count(const int64_t *dims_host, const int *inst_atoms, const int *inst_group, const int *a2i_off, const int *a2i,
+                  const int *group_i, const int *chan_i, const double *chan_d, const double *tab, const int *msidx,
+                  const double *objp, const int *types, int64_t R, int *hist, double *corr, double *delta, double *objective,
+                  int space, void *stream);
+/* run: every replica r starts from its own shuffle of types0 (N) and makes max_steps >= 0 swap attempts at temperature T, in
+ * launches of launch_steps steps (0: the library's choice; the cut changes no bit).  objectives (R) = every replica's best
+ * objective; winner (1) = the replica with the lowest, the lowest index on a tie; best_types (N) i32 and best_corr (C) are the
+ * winner's; all_best (R, N) u8 (may be NULL) = every replica's best types. */
+int mdh_sqs_run(const int64_t *dims_host, const int *inst_atoms, const int *inst_group, const int *a2i_off, const int *a2i,
+                const int *group_i, const int *chan_i, const double *chan_d, const double *tab, const int *msidx,
+                const double *objp, const int *types0, int64_t max_steps, double T, int64_t R, uint64_t seed, int64_t launch_steps,
+                int *winner, int *best_types, double *best_corr, double *objectives, unsigned char *all_best, int space,
+                void *stream);
+
 /* ---- _msd -------------------------------------------------------------- */
 /* Mean squared displacement of a trajectory.  pos (F, N, 3) f64, C-contiguous, UNWRAPPED positions of F >= 1 frames of N >= 1
  * atoms.  term(a, b) = (dx*dx + dy*dy) + dz*dz with dx = a.x - b.x, ..., every operation in IEEE binary64 without contraction.

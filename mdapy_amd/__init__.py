@@ -29,7 +29,8 @@ from .void_analysis import VoidAnalysis
 from .trajectory import Trajectory
 from .unwrap_trajectory import unwrap_trajectory
 from .vdw_radii import VDW_RADII, vdw_radius
-from .build_lattice import build_crystal
+from .build_lattice import build_crystal, build_hea, build_hea_fromsystem
+from .sqs import SQS
 from .create_polycrystal import CreatePolycrystal
 from .parallel import get_num_threads
 
@@ -38,5 +39,5 @@ __all__ = [
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
     "AtomicStrain", "CalculatorMP", "EAM", "NEP", "FIRE", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
     "Trajectory", "unwrap_trajectory", "VDW_RADII", "vdw_radius",
-    "build_crystal", "CreatePolycrystal", "get_num_threads",
+    "build_crystal", "build_hea", "build_hea_fromsystem", "SQS", "CreatePolycrystal", "get_num_threads",
 ]

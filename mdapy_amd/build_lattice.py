@@ -79,3 +79,39 @@ def build_crystal(name, structure, a, miller1=None, miller2=None, miller3=None, 
     pos = flat.reshape((-1, 3))
     frame = Frame({"x": pos[:, 0], "y": pos[:, 1], "z": pos[:, 2], "element": np.full(len(pos), name, dtype=object)})
     return System(data=frame, box=Box(_supercell(cell, nx, ny, nz)))
+
+
+def build_hea(element_list, element_ratio, structure, a, miller1=None, miller2=None, miller3=None, nx=1, ny=1, nz=1, c=None,
+              random_seed=None):
+    """a random alloy on one sublattice (src/mdapy/build_lattice.py:1032-1097): the crystal of ``build_crystal`` — standard
+    orientation only — with its sites dealt among ``element_list`` by ``build_hea_fromsystem``"""
+    lattice = build_crystal("X", structure, a, miller1=miller1, miller2=miller2, miller3=miller3, nx=nx, ny=ny, nz=nz, c=c)
+    return build_hea_fromsystem(lattice, element_list, element_ratio, random_seed=random_seed)
+
+
+def hea_counts(n_atoms, element_ratio):
+    """atoms per element, the reference's rule (src/mdapy/build_lattice.py:1136-1140): floor(N ratio), at least one atom of every
+    listed element, and the last element takes whatever is left"""
+    share = np.asarray(element_ratio, dtype=np.float64)
+    counts = np.floor(n_atoms * share).astype(int)
+    counts[(counts == 0) & (share > 1e-6)] = 1
+    counts[-1] = n_atoms - int(counts[:-1].sum())
+    return counts
+
+
+def build_hea_fromsystem(system, element_list, element_ratio, random_seed=None):
+    """``system`` with an element per atom (src/mdapy/build_lattice.py:1100-1148): ``hea_counts`` copies of each name, in list
+    order, shuffled by numpy's legacy generator (``np.random.seed`` + ``np.random.shuffle``), so a seed gives the reference's
+    alloy.  The system is changed in place and returned."""
+    kinds = len(element_list)
+    assert kinds > 1, "At least two elements are required to form an HEA."
+    assert len(set(element_list)) == kinds, "Each element in element_list must be unique."
+    assert len(element_ratio) == kinds, "element_list and element_ratio must have the same length."
+    total = float(np.sum(element_ratio))
+    assert abs(total - 1.0) < 1e-6, f"Element ratios must sum to 1 (got {total:.6f})."
+    names = np.repeat(np.array(element_list, dtype=object), hea_counts(system.N, element_ratio))
+    if random_seed is not None:
+        np.random.seed(int(random_seed))
+    np.random.shuffle(names)
+    system.update_data(system.data.with_columns(element=names))
+    return system

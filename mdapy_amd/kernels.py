@@ -39,6 +39,8 @@ from . import _rdf as rdf
 from . import _repeat_cell as repeat_cell
 from . import _sbo as sbo
 from . import _sfc as sfc
+# (not in NAMES either: the oracle has no SQS engine; its tests install a restatement as kernels.sqs)
+from . import _sqs as sqs
 # (not in NAMES either: the oracle has no atomic strain; its tests install a restatement as kernels.strain)
 from . import _strain as strain
 from . import _structure_entropy as structure_entropy
