@@ -204,6 +204,33 @@ int mdh_parse_table(const char *text, int64_t nbytes, int text_space, int64_t nr
  * (high, low word); the field converter itself: 0 converted, 1 undecided (host must redo), 2 not a number */
 int mdh_debug_text_pow5(int q, uint64_t *out2);
 int mdh_debug_parse_double(const char *s, int64_t len, double *out);
+/* The inverse (csrc/text_format.hip): nrows x ncol numeric columns -> the bytes of a text table, fields joined by one blank,
+ * rows ended by "\n"; floats as Python's format(v, ".10f") (exact, round-half-to-even; "NaN", "inf", "-inf" for the
+ * non-finite), integers in plain decimal.  kinds[c] (host): 0 f64, 1 f32, 2 i32, 3 i64, 4 coded string — an i32 column of
+ * codes into a table of names given on the HOST: name k of column c is name_blobs[c][name_offsets[c][k] ..
+ * name_offsets[c][k + 1]), k < name_counts[c] (the three arrays have ncol entries, read only where kinds[c] == 4; they may be
+ * NULL when no column is one).  columns[c], text (capacity bytes) and row_end (nrows: the offset one past each row's "\n")
+ * live in `space`.  status3 (host): [0] bytes of the table, [1] fields that cannot be formatted (a finite |x| >= 2^64, a
+ * code outside its table), [2] the capacity needed when the given one is too small, else 0.  When [1] or [2] is not zero
+ * NOT ONE BYTE of text or row_end is written (the return code is still MDH_OK).  MDH_ERR_ARG, before any device work: null
+ * pointers, nrows < 1, ncol outside 1..64, an unknown kind, a table of names whose offsets decrease, or more rows than 32-bit
+ * row offsets allow for this set of columns (2^31 - 1 over the longest possible row: format in chunks of rows). */
+int mdh_format_table(int64_t nrows, int ncol, const int *kinds, const void *const *columns, const char *const *name_blobs,
+                     const int *const *name_offsets, const int *name_counts, char *text, int64_t capacity, int64_t *row_end,
+                     int64_t *status3, int space, void *stream);
+/* What the writers do to positions before formatting: out_k = ((x - o0) m_0k + (y - o1) m_1k) + (z - o2) m_2k, unfused and in
+ * this order (origin3 and the row-major matrix9 on the HOST; matrix9 NULL: the shift alone).  The rotation into LAMMPS' axes
+ * of a general triclinic cell, the reduced coordinates of a POSCAR. */
+int mdh_shift_rotate(const double *x, const double *y, const double *z, int64_t N, const double *origin3, const double *matrix9,
+                     double *out_x, double *out_y, double *out_z, int space, void *stream);
+/* test hooks (run on the host, no GPU needed): the field converters the kernels use, compiled for the host.  out32 takes up to
+ * 32 bytes (no terminator); the return value is the length, or negative for "not formatted" (a finite |x| >= 2^64). */
+int mdh_debug_format_double(double v, char *out32);
+int mdh_debug_format_float(float v, char *out32);
+int mdh_debug_format_int64(int64_t v, char *out32);
+/* measuring hook: 0 the library's choice (a workgroup's span built in LDS and stored in 16-byte words where it fits),
+ * 1 every field straight to HBM (profiles/text_format.md compares the two) */
+int mdh_debug_set_format_variant(int v);
 /* test hook (runs on the host, no GPU needed): the rule by which the cell-assignment kernel groups the atoms of a 64-atom
  * slice under one atomic (csrc/assign_groups.hpp), applied to cells[0 .. n) slice by slice (a last short slice is padded
  * with negative cells).  head[i] = index, inside its slice, of the lane whose atomic serves atom i; count[i] = what that

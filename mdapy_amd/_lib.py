@@ -58,6 +58,12 @@ _SIGNATURES = {
     "mdh_parse_table": [vp, i64, cint, i64, cint, vp, vp, vp, i64, vp, cint, vp],
     "mdh_debug_text_pow5": [cint, vp],
     "mdh_debug_parse_double": [C.c_char_p, i64, vp],
+    "mdh_format_table": [i64, cint, vp, vp, vp, vp, vp, vp, i64, vp, vp, cint, vp],
+    "mdh_shift_rotate": [vp, vp, vp, i64, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_debug_format_double": [dbl, vp],
+    "mdh_debug_format_float": [C.c_float, vp],
+    "mdh_debug_format_int64": [i64, vp],
+    "mdh_debug_set_format_variant": [cint],
     "mdh_debug_assign_groups": [vp, i64, vp, vp, vp],
     "mdh_build_neighbor": [vp, vp, vp, i64, vp, vp, vp, dbl, vp, vp, vp, i64, cint, cint, vp],
     "mdh_slab_halo_select": [vp, vp, vp, i64, vp, vp, dbl, dbl, vp, vp, vp, vp, vp, vp, i64, cint, vp],

@@ -415,6 +415,7 @@ void warm_sfc(hipStream_t st);
 void warm_polycrystal(hipStream_t st);
 void warm_slab(hipStream_t st);
 void warm_text(hipStream_t st);
+void warm_text_format(hipStream_t st);
 }
 namespace mdh {
 __global__ void k_warm_runtime() {}
@@ -547,6 +548,7 @@ int mdh_warm(void)
     mdh::warm_polycrystal(nullptr);
     mdh::warm_slab(nullptr);
     mdh::warm_text(nullptr);
+    mdh::warm_text_format(nullptr);
     MDH_HIP(hipGetLastError());
     MDH_HIP(hipStreamSynchronize(nullptr));
     if (device < 64) done |= 1ull << device;

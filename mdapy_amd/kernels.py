@@ -44,6 +44,9 @@ from . import _sqs as sqs
 # (not in NAMES either: the oracle has no atomic strain; its tests install a restatement as kernels.strain)
 from . import _strain as strain
 from . import _structure_entropy as structure_entropy
+# (not in NAMES either: the oracle has no tokenizer or formatter; the readers and writers of load_save check both against Python's
+# own float() and format())
+from . import _text as text
 # (not in NAMES either: neither the reference nor the oracle has a compiled unwrap; its tests install a restatement as kernels.unwrap)
 from . import _unwrap as unwrap
 # (not in NAMES either: the oracle has no adapter for the void analysis; its tests install a restatement as kernels.void and as

@@ -9,7 +9,11 @@ where the atom table is converted: the reference slurps the file and calls a CSV
 parsed on the host (a few lines) and the table's bytes are streamed into HBM, tokenised and converted there
 (``_text.py`` / ``csrc/text.hip``, correctly rounded = ``float()``), so that a 10^7-atom file arrives as HBM-resident
 columns without a host-side table ever existing.  Files below ``DEVICE_MIN_BYTES`` — and any file on a machine without a
-GPU — take the host tokenizer instead (same values; it is I/O plumbing, not a compute fallback)."""
+GPU — take the host tokenizer instead (same values; it is I/O plumbing, not a compute fallback).
+
+The output side is further down: ``write_dump`` / ``write_dump_frame_to``, ``write_xyz``, ``write_data``, ``write_poscar``
+(``src/mdapy/load_save.py:1565-2017``) beside ``write_mp``, the inverse arrangement — headers on the host, the atom table
+formatted in HBM (``_text.py`` / ``csrc/text_format.hip``, every float exactly ``format(v, ".10f")``) and streamed to the file."""
 from __future__ import annotations
 
 import gzip
@@ -369,6 +373,367 @@ def write_mp(path, frame: Frame, box: Box, info: Optional[Dict[str, Any]] = None
             "origin": " ".join(repr(float(v)) for v in box.origin), "boundary": " ".join(str(int(v)) for v in box.boundary)}
     meta.update({k: str(v) for k, v in (info or {}).items()})
     pq.write_table(pa.table(arrays).replace_schema_metadata(meta), str(path))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the output side: LAMMPS dump and data, (extended) XYZ, POSCAR
+# ---------------------------------------------------------------------------------------------------------------------
+# The reference's writers (src/mdapy/load_save.py:1565-2017) print a few header lines and hand the atom table to a CSV writer
+# (separator " ", no header, float_precision=10).  Here the header is written on the host in the reference's wording, and the
+# table is formatted where its columns are: in HBM (``_text.format_chunks`` / csrc/text_format.hip), streamed to the file
+# through pinned buffers while the next piece is formatted — or, below DEVICE_MIN_ROWS rows and on a machine without a GPU, by
+# the host formatter (the same bytes; I/O plumbing, not a compute fallback).
+# Tables with fewer rows are formatted on the host.  Measured on an MI355X with six columns on the host (profiles/text_format.md):
+# the device path costs 3.7-4.0 ms up to 65 536 rows (uploads, three launches, two synchronisations, the pinned buffers), the
+# host formatter 0.56 us a row — 2.3 ms at 4 096 rows, 9.2 ms at 16 384: they cross near 6 800 rows.
+DEVICE_MIN_ROWS = 1 << 13
+
+
+def _num(v) -> str:
+    """a header number as the reference's f-strings print a numpy float64"""
+    return str(np.float64(v))
+
+
+def _in_hbm(col) -> bool:
+    return col._host_arr is None and col._dev is not None
+
+
+def _column_spec(col, device: bool):
+    """(array, kind, names) of one frame column for the table formatters; the array in HBM (``device``) or numpy"""
+    from . import _text
+    from .devarray import HArray
+
+    kind = np.dtype(col.dtype).kind
+    if kind in "OUS":
+        from . import policy
+
+        names, codes = policy.label_codes(col.to_numpy())
+        return codes, _text.CODED, _text.check_names(names)
+    if kind not in "iuf":
+        raise ValueError(f"column {col.name!r} of dtype {col.dtype} cannot be written to a text table")
+    native = {np.dtype(np.float64): _text.F64, np.dtype(np.float32): _text.F32, np.dtype(np.int32): _text.I32, np.dtype(np.int64): _text.I64}
+    dtype = np.dtype(col.dtype)
+    if dtype in native:
+        return (col.device_array() if device else col.to_numpy()), native[dtype], None
+    host = col.to_numpy()
+    if not device:
+        return host, (_text.F64 if kind == "f" else _text.I64), None
+    if kind == "f":
+        host, code = host.astype(np.float32), _text.F32  # (float16: every value is a float32)
+    elif dtype.itemsize < 4:
+        host, code = host.astype(np.int32), _text.I32
+    else:
+        if dtype == np.uint64 and host.size and host.max() >= 2 ** 63:
+            raise _text.Unformattable(int((host >= 2 ** 63).sum()))
+        host, code = host.astype(np.int64), _text.I64
+    return HArray.from_numpy(host), code, None
+
+
+def _rewindable(op) -> bool:
+    return type(op) in (io.BufferedWriter, io.BufferedRandom, io.FileIO, io.BytesIO)
+
+
+def _write_table(op, columns, rows=None) -> None:
+    """the rows of ``columns`` (frame Columns of equal length) as text into the binary file object ``op``"""
+    import tempfile
+
+    from . import _text
+
+    n = len(columns[0])
+    if n and have_gpu() and n >= DEVICE_MIN_ROWS:
+        try:
+            specs = [_column_spec(c, True) for c in columns]
+            pieces = _text.format_chunks([s[0] for s in specs], [s[1] for s in specs], [s[2] for s in specs], rows)
+            if _rewindable(op):
+                start = op.tell()
+                try:
+                    _text.stream_from_device(pieces, op)
+                except _text.Unformattable:
+                    op.seek(start)
+                    op.truncate()
+                    raise
+            else:  # (a handle that cannot take its bytes back — a gzip stream —: the text goes through a scratch file)
+                import shutil
+
+                with tempfile.TemporaryFile() as scratch:
+                    _text.stream_from_device(pieces, scratch)
+                    scratch.seek(0)
+                    shutil.copyfileobj(scratch, op, 1 << 24)
+            return
+        except _text.Unformattable:  # the device met a field it does not format: the whole table goes to the host formatter
+            pass
+    host_specs = [_column_spec(c, False) for c in columns]
+    if n:
+        _text.format_table_host([s[0] for s in host_specs], [s[1] for s in host_specs], [s[2] for s in host_specs], op)
+
+
+def _moved(frame: Frame, origin, matrix):
+    """columns x, y, z of ``frame`` minus ``origin`` and (``matrix`` given) times it: in HBM when they live there or the table is
+    going to be formatted there, on the host otherwise — the same bits either way"""
+    from . import _text
+    from .frame import Column
+
+    cols = [frame[c] for c in "xyz"]
+    n = len(cols[0])
+    device = have_gpu() and n and (all(_in_hbm(c) for c in cols) or n >= DEVICE_MIN_ROWS) and all(c.dtype == np.float64 for c in cols)
+    arrays = [c.device_array() for c in cols] if device else [np.asarray(c.to_numpy(), dtype=np.float64) for c in cols]
+    return [Column(name, a) for name, a in zip("xyz", _text.shift_rotate(*arrays, origin, matrix))]
+
+
+def _with_id(frame: Frame) -> Frame:
+    """``id`` = 1 .. N as the first column when the frame has none (the reference's ``with_row_index("id", offset=1)``)"""
+    if "id" in frame.columns:
+        return frame
+    n = frame.shape[0]
+    if have_gpu() and n >= DEVICE_MIN_ROWS:
+        from .devarray import HArray, torch
+
+        ids = HArray(torch().arange(1, n + 1, dtype=torch().int32 if n < 2 ** 31 else torch().int64, device="cuda"))
+    else:
+        ids = np.arange(1, n + 1, dtype=np.int32 if n < 2 ** 31 else np.int64)
+    cols = {"id": ids}
+    cols.update({k: frame[k] for k in frame.columns})
+    return Frame(cols)
+
+
+def _lammps_axes(frame: Frame, box: Box):
+    """a cell with a component above its diagonal is rotated into LAMMPS' axes (a along x, b in the xy plane), the positions with
+    it, and the origin moves to zero (load_save.py:1797-1811, 1964-1975)"""
+    m = box.box
+    if m[0, 1] != 0 or m[0, 2] != 0 or m[1, 2] != 0:
+        box, rotate = box.align_to_lammps_box()
+        x, y, z = _moved(frame, box.origin, rotate)
+        box.origin[:] = 0
+        frame = frame.with_columns(x=x, y=y, z=z)
+    return frame, box
+
+
+def _save(write, path, compress: bool, **kwargs) -> None:
+    """``write(file object, **kwargs)`` into ``path``, or gzipped into ``path`` (+ ``.gz`` when the name lacks it)"""
+    path = str(path)
+    if not compress:
+        with open(path, "wb") as op:
+            write(op, **kwargs)
+        return
+    with gzip.open(path if path.endswith(".gz") else path + ".gz", "wb") as op:
+        write(op, **kwargs)
+
+
+def _need(frame, names):
+    if not isinstance(frame, Frame):
+        raise TypeError("data must be a Frame")
+    for col in names:
+        if col not in frame.columns:
+            raise ValueError(f"data must contain {col} column")
+
+
+def write_dump_frame_to(op, box: Box, frame: Frame, timestep=0.0, rows=None) -> None:
+    """one LAMMPS dump frame into the open binary file ``op`` (load_save.py:1954-2017): ``write_dump`` writes one, a
+    ``Trajectory`` one after another"""
+    frame = _with_id(frame)
+    frame, box = _lammps_axes(frame, box)
+    keep = [c for c in frame.columns if np.dtype(frame[c].dtype).kind in "iuf" or c == "element"]  # numeric columns + `element`
+    frame = frame.select(keep)
+    bound = ["pp" if i == 1 else "ss" for i in box.boundary]
+    op.write(f"ITEM: TIMESTEP\n{timestep}\n".encode())
+    op.write(f"ITEM: NUMBER OF ATOMS\n{frame.shape[0]}\n".encode())
+    xlo, ylo, zlo = (np.float64(v) for v in box.origin)
+    xhi, yhi, zhi = xlo + box.box[0, 0], ylo + box.box[1, 1], zlo + box.box[2, 2]
+    xy, xz, yz = box.box[1, 0], box.box[2, 0], box.box[2, 1]
+    if xy != 0 or xz != 0 or yz != 0:
+        xlo_bound, xhi_bound = xlo + min(0.0, xy, xz, xy + xz), xhi + max(0.0, xy, xz, xy + xz)
+        ylo_bound, yhi_bound = ylo + min(0.0, yz), yhi + max(0.0, yz)
+        op.write(f"ITEM: BOX BOUNDS xy xz yz {bound[0]} {bound[1]} {bound[2]}\n".encode())
+        op.write(f"{_num(xlo_bound)} {_num(xhi_bound)} {_num(xy)}\n".encode())
+        op.write(f"{_num(ylo_bound)} {_num(yhi_bound)} {_num(xz)}\n".encode())
+        op.write(f"{_num(zlo)} {_num(zhi)} {_num(yz)}\n".encode())
+    else:
+        op.write(f"ITEM: BOX BOUNDS {bound[0]} {bound[1]} {bound[2]}\n".encode())
+        op.write(f"{_num(xlo)} {_num(xhi)}\n{_num(ylo)} {_num(yhi)}\n{_num(zlo)} {_num(zhi)}\n".encode())
+    op.write(("ITEM: ATOMS " + " ".join(frame.columns) + " \n").encode())
+    _write_table(op, [frame[c] for c in frame.columns], rows)
+
+
+def write_dump(path, frame: Frame, box: Box, timestep=0.0, compress: bool = False, rows=None) -> None:
+    """a single-frame LAMMPS dump file (load_save.py:1910-1952).  ``rows``: rows formatted per piece on the device path."""
+    _need(frame, ["type", "x", "y", "z"])
+    _save(write_dump_frame_to, path, compress, box=box, frame=frame, timestep=timestep, rows=rows)
+
+
+_XYZ_TRIPLES = [(("x", "y", "z"), "pos"), (("xu", "yu", "zu"), "unwrapped_position"), (("vx", "vy", "vz"), "vel"), (("fx", "fy", "fz"), "forces")]
+
+
+def _xyz_type(dtype) -> str:
+    kind = np.dtype(dtype).kind
+    if kind in "iu":
+        return "I"
+    if kind == "f":
+        return "R"
+    if kind in "OUS":
+        return "S"
+    raise ValueError(f"Unrecognised dtype {dtype} in extended XYZ output")
+
+
+def _xyz_properties(columns: List[str], dtypes) -> str:
+    """the ``Properties=`` token (the rules of load_save.py:201-273): a run x y z / xu yu zu / vx vy vz / fx fy fz of floats folds
+    into pos / unwrapped_position / vel / forces ``:R:3``, ``element`` is ``species``, a run ``base_0 base_1 ...`` of one dtype
+    folds into ``base:T:n``, everything else is ``name:T:1``"""
+    tokens, i = [], 0
+    while i < len(columns):
+        for triple, alias in _XYZ_TRIPLES:
+            if tuple(columns[i:i + 3]) == triple and all(_xyz_type(dtypes[i + j]) == "R" for j in range(3)):
+                tokens.append(f"{alias}:R:3")
+                i += 3
+                break
+        else:
+            cur = columns[i]
+            if cur == "element":
+                tokens.append(f"species:{_xyz_type(dtypes[i])}:1")
+                i += 1
+                continue
+            base, sep, idx = cur.rpartition("_")
+            run = 1
+            if sep and base and idx.isdigit() and int(idx) == 0:
+                while i + run < len(columns):
+                    nb, ns, ni = columns[i + run].rpartition("_")
+                    if not ns or nb != base or not ni.isdigit() or int(ni) != run or np.dtype(dtypes[i + run]) != np.dtype(dtypes[i]):
+                        break
+                    run += 1
+            if run >= 2:
+                tokens.append(f"{base}:{_xyz_type(dtypes[i])}:{run}")
+                i += run
+            else:
+                tokens.append(f"{cur}:{_xyz_type(dtypes[i])}:1")
+                i += 1
+    return "Properties=" + ":".join(tokens)
+
+
+def _write_xyz_to(op, box: Box, frame: Frame, classical: bool, rows=None, **kargs) -> None:
+    if classical:
+        op.write(f"{frame.shape[0]}\n".encode())
+        op.write("Classical XYZ file written by mdapy.\n".encode())
+        _write_table(op, [frame[c] for c in ("element", "x", "y", "z")], rows)
+        return
+    properties = _xyz_properties(frame.columns, [frame[c].dtype for c in frame.columns])
+    comments = ('Lattice="' + " ".join(_num(v) for v in box.box.flatten()) + '" ' + properties
+                + ' pbc="' + " ".join("T" if i == 1 else "F" for i in box.boundary) + '"'
+                + ' Origin="' + " ".join(_num(v) for v in box.origin) + '"')
+    for key, value in kargs.items():
+        if key.lower() not in ("lattice", "pbc", "properties", "origin"):
+            comments += f' {key}="{value}"' if key.lower() in ("virial", "bec", "stress") else f" {key}={value}"
+    op.write(f"{frame.shape[0]}\n".encode())
+    op.write(f"{comments}\n".encode())
+    _write_table(op, [frame[c] for c in frame.columns], rows)
+
+
+def write_xyz(path, frame: Frame, box: Box, classical: bool = False, compress: bool = False, rows=None, **kargs) -> None:
+    """an XYZ file (load_save.py:1565-1652): extended — Lattice, Properties, pbc, Origin and the extra keys in the comment line,
+    every column in the table — or ``classical``: ``element x y z`` alone"""
+    _need(frame, ["x", "y", "z", "element"])
+    _save(_write_xyz_to, path, compress, box=box, frame=frame, classical=classical, rows=rows, **kargs)
+
+
+def _write_poscar_to(op, box: Box, frame: Frame, reduced_pos: bool, selective_dynamics: bool, rows=None) -> None:
+    from . import _text, policy
+    from .frame import PermutedColumn
+
+    if selective_dynamics:
+        for col in ("sdx", "sdy", "sdz"):
+            if col not in frame.columns:
+                raise ValueError(f"data must contain {col} if selective_dynamics=True")
+    names, codes = policy.label_codes(frame["element"].to_numpy())
+    names, codes = _text.check_names(names), np.asarray(codes)  # (the names go into the header line, blank-separated)
+    order = np.argsort(codes, kind="stable")  # by element; atoms of one element keep their order
+    counts = np.bincount(codes, minlength=len(names))
+    x, y, z = _moved(frame, box.origin, box.inverse_box if reduced_pos else None)
+    table = [x, y, z] + ([frame[c] for c in ("sdx", "sdy", "sdz")] if selective_dynamics else [])
+    perm = order.astype(np.int32)
+    if any(_in_hbm(c) for c in table):  # (columns in HBM are gathered there: frame.PermutedColumn)
+        from .devarray import HArray
+
+        perm = HArray.from_numpy(perm)
+    table = [PermutedColumn(c, perm) for c in table]
+    op.write("# VASP POSCAR file written by mdapy.\n".encode())
+    op.write("1.0000000000\n".encode())
+    for k in range(3):
+        op.write("{:.10f} {:.10f} {:.10f}\n".format(*(float(v) for v in box.box[k])).encode())
+    op.write(("".join(f"{name} " for name in names) + "\n").encode())
+    op.write(("".join(f"{int(c)} " for c in counts) + "\n").encode())
+    if selective_dynamics:
+        op.write("Selective dynamics\n".encode())
+    op.write(("Direct\n" if reduced_pos else "Cartesian\n").encode())
+    _write_table(op, table, rows)
+
+
+def write_poscar(path, frame: Frame, box: Box, reduced_pos: bool = False, selective_dynamics: bool = False, compress: bool = False,
+                 rows=None) -> None:
+    """a VASP POSCAR file (load_save.py:1654-1752): atoms grouped by element (a STABLE sort: atoms of one element keep their
+    order, which the reference leaves open), positions minus the origin, Cartesian or reduced"""
+    _need(frame, ["element", "x", "y", "z"])
+    _save(_write_poscar_to, path, compress, box=box, frame=frame, reduced_pos=reduced_pos, selective_dynamics=selective_dynamics, rows=rows)
+
+
+def _write_data_to(op, box: Box, frame: Frame, element_list, num_type, data_format: str, rows=None) -> None:
+    from .atomic_temperature import STANDARD_ATOMIC_WEIGHT
+
+    frame = _with_id(frame)
+    frame, box = _lammps_axes(frame, box)
+    if data_format not in ["atomic", "charge"]:
+        raise ValueError(f"Unrecognized data format: {data_format}. Only support atomic and charge")
+    types = frame["type"]
+    type_max = int(types.device_array().max() if _in_hbm(types) else types.to_numpy().max())
+    if num_type is None:
+        num_type = type_max
+    elif num_type < type_max:
+        raise ValueError(f"num_type ({num_type}) is less than the largest type in data ({type_max})")
+    if element_list is not None:
+        if len(element_list) < num_type:
+            raise ValueError(f"element_list has {len(element_list)} entries but num_type is {num_type}; need at least {num_type}")
+        if len(element_list) > num_type:
+            import warnings
+
+            warnings.warn(f"element_list has {len(element_list)} entries but num_type={num_type}; writing only the first {num_type} elements.",
+                          stacklevel=2)
+            element_list = list(element_list)[:num_type]
+        for name in element_list:
+            if name not in STANDARD_ATOMIC_WEIGHT:
+                raise ValueError(f"Unrecognized element name {name}")
+    op.write("# LAMMPS data file written by mdapy.\n\n".encode())
+    op.write(f"{frame.shape[0]} atoms\n{num_type} atom types\n\n".encode())
+    origin = [np.float64(v) for v in box.origin]
+    for k, axis in enumerate("xyz"):
+        op.write(f"{_num(origin[k])} {_num(origin[k] + box.box[k, k])} {axis}lo {axis}hi\n".encode())
+    xy, xz, yz = box.box[1, 0], box.box[2, 0], box.box[2, 1]
+    if xy != 0 or xz != 0 or yz != 0:
+        op.write(f"{_num(xy)} {_num(xz)} {_num(yz)} xy xz yz\n".encode())
+    op.write("\n".encode())
+    if element_list is not None:
+        op.write("Masses\n\n".encode())
+        for k, name in enumerate(element_list, start=1):
+            op.write(f"{k} {_num(STANDARD_ATOMIC_WEIGHT[name])} # {name}\n".encode())
+        op.write("\n".encode())
+    op.write(f"Atoms # {data_format}\n\n".encode())
+    if data_format == "charge" and "q" not in frame.columns:
+        n = frame.shape[0]
+        if have_gpu() and n >= DEVICE_MIN_ROWS:
+            from .devarray import HArray
+
+            frame = frame.with_columns(q=HArray.full((n,), 0.0, np.float64))
+        else:
+            frame = frame.with_columns(q=np.zeros(n, np.float64))
+    wanted = ["id", "type", "x", "y", "z"] if data_format == "atomic" else ["id", "type", "q", "x", "y", "z"]
+    _write_table(op, [frame[c] for c in wanted], rows)
+    if all(c in frame.columns for c in ("vx", "vy", "vz")):
+        op.write("\nVelocities\n\n".encode())
+        _write_table(op, [frame[c] for c in ("id", "vx", "vy", "vz")], rows)
+
+
+def write_data(path, frame: Frame, box: Box, element_list=None, num_type=None, data_format: str = "atomic", compress: bool = False,
+               rows=None) -> None:
+    """a LAMMPS data file (load_save.py:1754-1908): header, optional Masses block, ``Atoms # atomic`` (id type x y z) or
+    ``# charge`` (id type q x y z, q = 0.0 when the frame has none), and a Velocities section when vx vy vz are there"""
+    _need(frame, ["type", "x", "y", "z"])
+    _save(_write_data_to, path, compress, box=box, frame=frame, element_list=element_list, num_type=num_type, data_format=data_format, rows=rows)
 
 
 def read_file(path: str, fmt: Optional[str] = None):

@@ -407,6 +407,42 @@ class System:
                                                    z=x * m[0, 2] + y * m[1, 2] + z * m[2, 2] + new_box.origin[2])
         self.box = new_box  # (the setter forgets the neighbor list)
 
+    # ---- the writers (src/mdapy/system.py:939-1107): headers on the host, the atom table formatted where its columns live
+    def write_mp(self, output_name):
+        from .load_save import write_mp
+
+        write_mp(output_name, self.data, self.box, self.global_info)
+
+    def write_xyz(self, output_name, classical=False, compress=False):
+        from .load_save import write_xyz
+
+        write_xyz(output_name, self.data, self.box, classical, compress, **self.global_info)
+
+    def write_poscar(self, output_name, reduced_pos=False, selective_dynamics=False, compress=False):
+        from .load_save import write_poscar
+
+        write_poscar(output_name, self.data, self.box, reduced_pos=reduced_pos, selective_dynamics=selective_dynamics, compress=compress)
+
+    def write_data(self, output_name, element_list=None, num_type=None, data_format="atomic", compress=False):
+        """with ``element_list`` and an ``element`` column, ``type`` is derived from the list's order for this file alone"""
+        from .load_save import write_data
+
+        data = self.data
+        if element_list is not None and "element" in data.columns:
+            names = data["element"].to_numpy()
+            present, codes = policy.label_codes(names)
+            for name in present:
+                assert name in element_list, f"element_list must include element {name!r}."
+            order = {name: k for k, name in enumerate(element_list, start=1)}
+            lut = np.array([order[name] for name in present], dtype=np.int32)
+            data = data.with_columns(type=lut[np.asarray(codes)])
+        write_data(output_name, data, self.box, element_list=element_list, num_type=num_type, data_format=data_format, compress=compress)
+
+    def write_dump(self, output_name, timestep=0, compress=False):
+        from .load_save import write_dump
+
+        write_dump(output_name, self.data, self.box, timestep=timestep, compress=compress)
+
     def delete_overlap(self, rc, max_neigh=None):
         """remove every atom that has a SURVIVING neighbour of smaller index closer than ``rc``; returns how many went
         (system.py:1414-1490: a sweep in index order).  The sweep's answer is the unique solution of

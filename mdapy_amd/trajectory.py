@@ -5,9 +5,10 @@ One pass over the file finds the byte range of every frame (a dump frame starts 
 is a count line, a comment line and that many rows); every frame is then parsed by the code the single-frame readers of
 ``load_save`` use, so a large frame's table is tokenised in HBM and a small one on the host, as there.
 
-Not built: ``save``, ``XYZTrajectory``, the ``vacuum`` padding and the progress bar — ``verbose`` is accepted
-and prints nothing; ``fast_mode`` is accepted for XYZ and changes nothing, there being one reader.  ``positions()`` is this
-project's own addition, not the reference's."""
+``save`` writes the dump format (frame after frame through ``load_save.write_dump_frame_to``).  Not built:
+saving as XYZ, ``XYZTrajectory``, the ``vacuum`` padding and the progress bar — ``verbose`` is accepted and prints nothing;
+``fast_mode`` is accepted for XYZ and changes nothing, there being one reader.  ``positions()`` is this project's own
+addition, not the reference's."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -202,6 +203,35 @@ class Trajectory:
 
     def concatenate(self, other: "Trajectory") -> "Trajectory":
         return type(self)(systems=[*self._systems, *other._systems])
+
+    def save(self, filename: str, frames=None, mode: str = "w", format: Optional[str] = None) -> None:
+        """write the frames — all of them, one (an int) or some (a list of ints) — as a multi-frame LAMMPS dump file, one frame
+        after another through ``load_save.write_dump_frame_to``; ``mode='a'`` appends to an existing file; a name that ends in
+        ``.gz`` is written gzipped.  Each frame's ``ITEM: TIMESTEP`` is its ``global_info['timestep']`` as an integer, 0 without
+        one (trajectory.py:1147-1159, 1257-1313)."""
+        if frames is None:
+            chosen = self._systems
+        elif isinstance(frames, int):
+            chosen = [self._systems[frames]]
+        else:
+            chosen = [self._systems[i] for i in frames]
+        if mode not in ("w", "a"):
+            raise ValueError(f"mode must be 'w' or 'a', got {mode!r}")
+        kind = format or _infer_format(filename)
+        if kind == "xyz":
+            raise NotImplementedError("Trajectory.save writes the LAMMPS dump format only: the reference's multi-frame XYZ has a header "
+                                      "style of its own (and a vacuum option) that is not built here. Use format='dump', or write "
+                                      "single frames with System.write_xyz.")
+        if kind != "dump":
+            raise ValueError(f"Unsupported trajectory format: {kind!r}")
+        with load_save._open(str(filename), mode + "b") as op:
+            for one in chosen:
+                step = one.global_info.get("timestep", 0) if one.global_info else 0
+                try:
+                    step = int(step)
+                except (TypeError, ValueError):
+                    step = 0
+                load_save.write_dump_frame_to(op, one.box, one.data, step)
 
     # ---- analyses
     def unwrap(self) -> "Trajectory":
