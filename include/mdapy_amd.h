@@ -145,6 +145,32 @@ int mdh_debug_grid_plan(const int64_t *in24, const double *in6, int *out15);
  * plan8 = {tile cells in x/y, in z, halo atoms per tile, LDS bytes, box full of atoms, 1000 * atoms per cell,
  * cells of the occupied region, 1 if a plan was made since the last query}; bit 8 of plan8[4]: the build's cell grid was a slot grid. */
 int mdh_debug_neighbor_plan(int *plan8);
+/* test hook: what a pass over a built cell grid decides before it enqueues anything (csrc/neighbor_plan.hpp: plan_lane,
+ * lane_plan_hook, plan_lane_launch, plan_tiled), on the host: no device is touched.
+ * in_i (19):
+ *   [0], [1], [2]  cells per axis, [3] cells, [4] grid mode (0: rc-wide cells)
+ *   [5], [6], [7]  1: the axis is periodic, [8] 1: a triclinic box
+ *   [9]  atoms, [10] slots of a row (1 when counting)
+ *   [11] 1: the fused CNA label is wanted, [12] 1: counts only
+ *   [13], [14] planes of axis 0 the grid was built over (0, 0: all), [15], [16] planes whose atoms want rows (0, 0: all)
+ *   [17] tiles the previous build listed for the slice pass (-1: not known)
+ *   [18] 1: through the calling thread's memo of its last plan, as a build does (this also sets what mdh_debug_neighbor_plan
+ *        reports on that thread); 0: the planner itself
+ * in_d (16): [0..8] box vectors (rows), [9..11] origin, [12..14] perpendicular thicknesses, [15] cutoff
+ * stats (99): the signature's statistics: [0] cells of the occupied region, [1 + len] 3-cell z-runs of that length
+ * out (46); the values are integers carried exactly, [6] and [7] single-precision numbers carried exactly:
+ *   [0], [1] tile cells in x/y and in z ([0] = 0: the tile kernel does not take the call), [2] halo atoms per tile, [3] 1: one-byte
+ *   tickets, [4] workgroups per CU, [5] rows per wave, [6] the scan's constant, [7] its band, [8] 1: all tiles are live,
+ *   [9] cells of the occupied region, [10] 0 or the refusal (-1, -3, -4, -5, -6, -7), [11] LDS bytes, [12] 1000 * atoms per cell,
+ *   [13], [14] refusal -5: runs of 89 atoms or more, all runs
+ *   [15..22] the words mdh_debug_neighbor_plan reports for this plan
+ *   launch geometry (zero without a plan): [23], [24], [25] tiles per axis, [26] tiles, [27] first pass over 0 all tiles, 1 the window's,
+ *   2 the list of live ones, [28] first tile, [29] tile planes of the run, [30] workgroups per XCD chunk, [31] grid, [32] 1: a walked
+ *   launch stands by, [33] 1: the slice pass runs, [34] slices per tile, [35] tiles along z of the slice pass, [36] entries the
+ *   mop-up's list may hold, [37] its tile's cells in z, [38] its tiles along z, [44], [45] centre planes as the kernel compares them
+ *   [39], [40] the round-1 tiled kernel's tile in x/y ([39] = 0: not applicable) and in z, [41] 1: image shifts per cell, [42] 1: all
+ *   tiles are live, [43] cells of the occupied region */
+int mdh_debug_lane_plan(const int64_t *in_i, const double *in_d, const int *stats, double *out);
 /* test hook (host only): the tile kernel's byte table of run offsets for a tile of txy x txy x tz cells (neighbor_lane.hip,
  * run_offset_table): out3 = {bytes of runs 0-3, bytes of runs 4-7, the bias added to the centre's halo cell}.  MDH_ERR_ARG: the
  * halo of such a tile has more cells than a workgroup has threads, no launch takes that shape. */

@@ -45,6 +45,7 @@ _SIGNATURES = {
     "mdh_debug_slot_grid_rule": [cint, cint, cint, cint, i64, i64, cint, cint, cint],
     "mdh_debug_grid_plan": [vp, vp, vp],
     "mdh_debug_neighbor_plan": [vp],
+    "mdh_debug_lane_plan": [vp, vp, vp, vp],
     "mdh_debug_run_offset_table": [cint, cint, vp],
     "mdh_debug_set_fcna_variant": [cint],
     "mdh_debug_track_counters": [cint],

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "grid_plan.hpp"
+#include "neighbor_plan.hpp"
 #include <atomic>
 #include <cmath>
 
@@ -23,8 +24,7 @@ struct Grid {
 //   atom code      (m + 15) per axis, 5 bits each, m in [-14, 14] (more: the build's flags[0], the thread-per-atom kernel)
 //   cell code      (n + 1) per axis, 2 bits each: the candidate's cell seen from the tile, n in {-1, 0, 1}
 //   combined code  (n + m + 16) per axis, 5 bits each — fits the 16-bit LDS entry of a staged atom
-namespace img {
-constexpr int MAX_M = 14;
+namespace img { // (MAX_M = 14: neighbor_plan.hpp)
 constexpr int ATOM_NEUTRAL = 15 | (15 << 5) | (15 << 10);
 constexpr int CELL_NEUTRAL = 1 | (1 << 2) | (1 << 4);
 constexpr int NEUTRAL = 16 | (16 << 5) | (16 << 10); // combined code "no shift"
@@ -124,13 +124,7 @@ inline SortedView view_of(const CellGrid &cg)
 int ensure_unpacked(Scope &sc, CellGrid &cg, int64_t N); // xs, ys, zs, mvs from pk (no-op when they exist)
 
 // neighbor_tiled.hip: the round-1 LDS-tiled kernel (double-precision scan, any run length); serves the cells too full for neighbor_lane.hip
-struct TiledPlan {
-    int tile;        // cells per tile edge in x and y; 0 = not applicable
-    int tile_z;      // cells per tile edge in z
-    bool cellshift;  // every periodic axis has >= 7 cells: per-cell image shifts may replace the minimum-image search
-    bool full;       // every 4x4x4 block of cells holds atoms (last known occupancy): all tiles are live
-    int64_t occupied; // cells of the occupied region (last known)
-};
+// (TiledPlan, plan_tiled: neighbor_plan.hpp)
 // what the LDS-tiled kernel leaves to the thread-per-atom kernel: tiles whose halo did not fit in LDS
 // (flag[t] != 0; *any counts them).  flag == nullptr: no filtering (the thread-per-atom kernel does everything).
 struct TileFilter {
@@ -145,8 +139,6 @@ struct TileFilter {
     int *listed_sink = nullptr; // != nullptr: the list is the tile kernel's FIRST pass's (no slice pass ran); the mop-up writes its length here (GridStats::listed_sink)
     const unsigned *big_stamp = nullptr; unsigned big_gen = 0; int *big_sink = nullptr; // CellGrid::big_sink: published by the pass's last kernel
 };
-// occupied_cells: cells of the occupied region (GridStats::v[0]); 0 = assume all of them
-TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells);
 
 // What one pass over a built cell grid is to leave behind (neighbor.hip neighbor_pass and the kernels' launchers)
 struct RowsRequest {
@@ -171,23 +163,7 @@ int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, 
                           const RowsRequest &rows, TileFilter &tf);
 
 // neighbor_lane.hip: LDS tiles, one thread per centre atom, single-precision pruning (see the file header)
-struct GridStats {
-    static constexpr int NBIN = 99; // v[0] = cells of the occupied region; v[1 + len] = 3-cell z-runs of that length (98: longer than 96)
-    int v[NBIN];
-    int last_listed = -1;   // tiles the first pass of the previous build with this (N, grid) listed for the second (-1: not known)
-    int *listed_sink = nullptr; // pinned host word THIS build writes that count to (device-visible): its second pass, or, when none is launched, its mop-up (TileFilter::listed_sink)
-};
-struct LanePlan {
-    int txy, tz;      // tile shape in cells; txy == 0: not applicable
-    int cap;          // atoms a tile's halo may hold in LDS
-    bool tk8;         // rows of at most 16 slots: one-byte tickets, lean LDS layout, rows written by the centre's lane
-    int wgs;          // workgroups per CU the LDS budget was cut for
-    int rw;           // rows (centres) a wave works on at a time: 64, fewer for long rows in dense cells
-    float mid, T;     // single-precision scan: the constant c subtracted from d2 (a little below rc^2) and the width W of the band above it
-    int last_listed = -1; int *listed_sink = nullptr; // GridStats: sizes the second pass's grid
-    bool full;        // every 4x4x4 block of cells holds atoms (last known statistics): all tiles are live
-    int64_t occupied; // cells of the occupied region (last known)
-};
+// (GridStats, LanePlanIn, LanePlan, plan_lane: neighbor_plan.hpp)
 // What the builds of one (N, grid, device) signature leave for the next one: a neighbor build steers itself by what the previous
 // build of the same system reported.  One heap object per signature, never freed (cell_grid.hip grid_feedback), reached through
 // CellGrid::fb.  Every word arrives when the device gets there: a build that reads an old answer is a slower one, never a wrong one.
@@ -206,9 +182,12 @@ struct GridFeedback {
 };
 // the statistics of cg's signature (cg.fb), counted on the device when they are stale
 int grid_stats_hint(Scope &sc, const CellGrid &cg, GridStats *out);
-LanePlan plan_lane(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count);
+// what plan_lane reads, from the box, the grid and the statistics
+LanePlanIn lane_plan_in(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count);
+// plan_lane behind the thread's memo of its last plan; fills the thread's report (mdh_debug_neighbor_plan, lane_last_listed)
+LanePlan plan_lane_memo(const LanePlanIn &in, const GridStats &gs);
 int lane_last_listed(); // tiles listed for the slice pass as last seen when a plan was made (mdh_debug_counters)
-int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, int64_t N, const DBox &b, double rc,
+int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, const GridStats &gs, int64_t N, const DBox &b, double rc,
                          const RowsRequest &rows, TileFilter &tf);
 // neighbor.hip, for other units of the library (knn.hip): the rows of a cutoff build on device arrays — its own cell grid, pads
 // written (-1 / rc + 1), counts that keep running past M — enqueued on the Scope's stream.  ids_only: RowsRequest::ids_only

@@ -297,26 +297,31 @@ static int neighbor_pass(Scope &sc, const CellGrid &cg, const DBox &b, int64_t N
     cg.flags_fresh = false;
     TileFilter tf{};
     tf.big_stamp = cg.big_stamp; tf.big_gen = cg.big_gen; tf.big_sink = cg.big_sink;
-    bool done = false;
+    const int variant = g_neighbor_variant;
     GridStats gs; // both planners size their tiles by the signature's statistics
-    if (g_neighbor_variant != 1) MDH_TRY(grid_stats_hint(sc, cg, &gs));
-    if (g_neighbor_variant == 0) { // tile kernel (orthogonal and triclinic boxes); the thread-per-atom code below then only mops up what it listed
-        const bool cna = rows.pattern && !count;
-        const LanePlan lp = plan_lane(b, cg.g, N, count ? 1 : rows.M, gs, rc, cna, count);
-        if (lp.txy) {
-            if (cna) tf.cna_todo = rows.todo;
-            MDH_TRY(launch_neighbor_lane(sc, cg, lp, N, b, rc, rows, tf));
-            done = true;
-            out.labelled = cna;
-        }
+    if (variant != 1) MDH_TRY(grid_stats_hint(sc, cg, &gs));
+    const bool cna = rows.pattern && !count;
+    LanePlan lp{};
+    if (variant == 0) lp = plan_lane_memo(lane_plan_in(b, cg.g, N, count ? 1 : rows.M, gs, rc, cna, count), gs);
+    TiledPlan tp{};
+    if (!lp.txy && variant != 1) { // (the tile kernel's plan, where there is one, is taken whatever this would say)
+        TiledPlanIn ti{};
+        for (int d = 0; d < 3; ++d) { ti.nc[d] = cg.g.nc[d]; ti.pbc[d] = b.pbc[d]; }
+        ti.mode = cg.g.mode; ti.tri = b.tri; ti.ncell = cg.g.ncell; ti.N = N; ti.M = rows.M; ti.occupied_cells = gs.v[0];
+        tp = plan_tiled(ti);
     }
-    // cells too full for the kernel above (or forced): the round-1 tiled kernel (a slot grid it does not read: the thread-per-atom kernel then)
-    if (!done && !count && g_neighbor_variant != 1 && !b.tri && !cg.slot_cap) {
-        const TiledPlan plan = plan_tiled(b, cg.g, N, rows.M, gs.v[0]);
-        if (plan.tile) {
-            MDH_TRY(ensure_unpacked(sc, const_cast<CellGrid &>(cg), N));
-            MDH_TRY(launch_neighbor_tiled(sc, cg, plan, N, b, rc, rows, tf));
-        }
+    switch (choose_rows_front(variant, count, b.tri != 0, cg.slot_cap != 0, lp.txy != 0, tp.tile != 0)) {
+    case RowsFront::LANE:
+        if (cna) tf.cna_todo = rows.todo;
+        MDH_TRY(launch_neighbor_lane(sc, cg, lp, gs, N, b, rc, rows, tf));
+        out.labelled = cna;
+        break;
+    case RowsFront::TILED:
+        MDH_TRY(ensure_unpacked(sc, const_cast<CellGrid &>(cg), N));
+        MDH_TRY(launch_neighbor_tiled(sc, cg, tp, N, b, rc, rows, tf));
+        break;
+    case RowsFront::ATOMS_ONLY:
+        break;
     }
     if (count) launch_neighbor<0>(st, cg, N, b, rc, nullptr, nullptr, rows.nn, 1, rows.max_count, tf);
     else if (rows.pads == RowsRequest::WRITE_PADS) launch_neighbor<2>(st, cg, N, b, rc, rows.verlet, rows.dist, rows.nn, rows.M, nullptr, tf);

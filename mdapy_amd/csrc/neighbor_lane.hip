@@ -46,6 +46,12 @@
 // ones carry their image number in their record, grid.hpp img::), max_neigh > 128 (> 64 where a cell holds more than 19.5 atoms),
 // grids where more than 5 % of the runs hold 89 atoms or more.
 //
+// What the host decides before the launches — whether the kernel takes a call, the tile shape, the LDS budget, the instance, the
+// decision band (plan_lane), and the launch geometry: all tiles, a window or a list, the grids, the stand-by launch, the slice pass
+// (plan_lane_launch) — lives in neighbor_plan.hpp, a header without HIP that the host tests run (tests/test_neighbor_plan.py through
+// mdh_debug_lane_plan, tests/native/neighbor_plan_host.cpp).  This file keeps the kernels, the statistics' I/O (grid_stats_hint), the
+// thread's memo of its last plan (plan_lane_memo) and the launcher, which allocates and enqueues from those structs.
+//
 // Measured (10 061 824-atom FCC Cu, rc = 0.854 a, M = 16; DESIGN.md 3a has the counters, the per-phase time stamps of the
 // MDH_STAMPS build and the tables of what moved the kernel and what was built and not kept): round-1 tiled kernel 1.78 ms,
 // round 2 of this kernel 1.14 ms, now 0.92 ms.
@@ -63,13 +69,7 @@
 namespace mdh {
 namespace lane {
 
-// A workgroup is NW waves: 256 threads, four workgroups per CU.  A tile has at most one halo cell per thread.
-constexpr int NW = 4;
-constexpr int CEN_CAP = 80 * NW; // centre atoms a tile may hold
-// tickets of a row + the spare slot, rounded up (rows are read back four tickets at a time).  (cna_rows: 28 bytes, room for a centre's
-// bond rows — built, and dropped: the 2 KB cost the headline tile 49 atoms of room, 169 of its 51 200 tiles went to the slice pass
-// (33 us), and since cna_counts_words fetches no row by a computed index nothing needs them)
-__host__ __device__ constexpr int ticket_row(int M, bool cna_rows) { return (cna_rows && ((M + 4) & ~3) < 28) ? 28 : ((M + 4) & ~3); }
+// (NW waves of a workgroup, CEN_CAP centre atoms of a tile, ticket_row: neighbor_plan.hpp, shared with the planner)
 static constexpr int NEUTRAL = img::CELL_NEUTRAL;  // a halo cell's image code "no shift" (grid.hpp img::)
 static constexpr int NEUTRAL3 = img::NEUTRAL;      // combined code "no shift"
 
@@ -135,8 +135,10 @@ static Shape make_shape(int txy, int tz, int nt1, int nt2)
 typedef __attribute__((address_space(3))) unsigned char lds_byte;
 typedef int Int4 __attribute__((ext_vector_type(4))); // 16 bytes of a row (nontemporal vector stores take clang vector types)
 
-static int g_last_plan[8]; // test hook (mdh_debug_neighbor_plan)
-static int g_last_listed = -1; // tiles the previous build with the last plan's (N, grid) listed for the slice pass (mdh_debug_counters)
+// The thread's report of its last plan (plan_lane_memo): the test hook's words (mdh_debug_neighbor_plan, lane_plan_hook) and the
+// tiles the previous build with that plan's (N, grid) listed for the slice pass (mdh_debug_counters)
+static thread_local int g_last_plan[8];
+static thread_local int g_last_listed = -1;
 #ifdef MDH_STAMPS
 __device__ unsigned long long g_stamps[65536 * 8];
 #define STAMP(k) do { if (tid == 0 && !parent && tile.id < 65536) g_stamps[tile.id * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -1295,233 +1297,66 @@ int grid_stats_hint(Scope &sc, const CellGrid &cg, GridStats *out)
     return MDH_OK;
 }
 
-namespace lane {
-
-// tk8: one-byte tickets, else two-byte ones; rows of (M + 1) tickets rounded up to a multiple of four; rw rows per wave
-static size_t lds_bytes(int cap, int64_t M, bool tk8, int rw, bool fcna = false)
+LanePlanIn lane_plan_in(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count)
 {
-    const size_t wave = std::max<size_t>((size_t)rw * (size_t)ticket_row((int)M, false) * (tk8 ? 1 : 2), 256); // (the kernel's wstride)
-    const size_t tk = (size_t)NW * wave;
-    return (size_t)cap * 16 + (size_t)cap * 16 + (size_t)cap * 8 + (size_t)CEN_CAP * 4 + (size_t)(cap + (cap & 1)) * 2 + ((tk + 15) & ~(size_t)15);
+    LanePlanIn in{};
+    for (int d = 0; d < 3; ++d) { in.nc[d] = g.nc[d]; in.pbc[d] = b.pbc[d]; in.o[d] = b.o[d]; in.thick[d] = b.thick[d]; }
+    for (int d = 0; d < 9; ++d) in.h[d] = b.h[d];
+    in.ncell = g.ncell; in.mode = g.mode; in.tri = b.tri; in.N = N; in.M = M; in.rc = rc; in.fcna = fcna; in.count = count;
+    for (int q = 0; q < GridStats::NBIN; ++q) in.v[q] = gs.v[q];
+    return in;
 }
 
-} // namespace lane
-
-// reason (negative) the tile kernel cannot take a call with this box, grid and row width; 0: it can
-static int lane_refusal(const DBox &b, const Grid &g, int64_t M)
+// The planning itself is neighbor_plan.hpp (plan_lane): a few microseconds of a step that is 70 us of host time at 4 000 atoms.  The
+// last plan of the thread is kept with its inputs and handed out again when they are the same; the thread's report follows every call.
+LanePlan plan_lane_memo(const LanePlanIn &in, const GridStats &gs)
 {
-    if (g.mode != 0 || M <= 0 || M > 128) return -1;
-    for (int d = 0; d < 3; ++d)
-        if (g.nc[d] < (b.pbc[d] ? 7 : 4)) return -3; // image numbers from the cell pair need >= 7 cells; skipping the far side of an open axis >= 4
-    return 0;
-}
-
-static LanePlan plan_lane_fresh(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count);
-
-// The plan is a function of the box, the grid, N, M, rc and the run-length / occupancy statistics — in a trajectory the same
-// from call to call — and the search below walks ~800 tile shapes: a few microseconds of a step that is 70 us of host time at
-// 4 000 atoms.  The last plan of the thread is kept with its inputs and handed out again when they are the same.
-LanePlan plan_lane(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count)
-{
-    struct Key { int nc[3], pbc[3], tri; int64_t N, M; double rc, o[3], h[9], thick[3]; int fcna, count; int v[GridStats::NBIN]; };
-    struct Memo { bool set = false; Key key; LanePlan plan; int hook[8]; };
+    struct Memo { bool set = false; LanePlanIn in; LanePlan plan; };
     static thread_local Memo memo;
-    Key k;
-    std::memset(&k, 0, sizeof(k)); // (padding bytes too: the keys are compared as bytes)
-    for (int d = 0; d < 3; ++d) { k.nc[d] = g.nc[d]; k.pbc[d] = b.pbc[d]; k.o[d] = b.o[d]; k.thick[d] = b.thick[d]; }
-    for (int d = 0; d < 9; ++d) k.h[d] = b.h[d];
-    k.tri = b.tri; k.N = N; k.M = M; k.rc = rc; k.fcna = fcna; k.count = count;
-    for (int q = 0; q < GridStats::NBIN; ++q) k.v[q] = gs.v[q];
-    if (memo.set && std::memcmp(&k, &memo.key, sizeof(k)) == 0) {
-        LanePlan p = memo.plan;
-        p.last_listed = gs.last_listed; // (the two fields that are not the plan's own)
-        p.listed_sink = gs.listed_sink;
-        lane::g_last_listed = gs.listed_sink ? *(volatile int *)gs.listed_sink : gs.last_listed;
-        for (int q = 0; q < 8; ++q) lane::g_last_plan[q] = memo.hook[q];
-        return p;
+    if (!memo.set || std::memcmp(&in, &memo.in, sizeof(in)) != 0) {
+        memo.plan = plan_lane(in);
+        memo.in = in;
+        memo.set = true;
     }
-    const LanePlan p = plan_lane_fresh(b, g, N, M, gs, rc, fcna, count);
-    memo.key = k;
-    memo.plan = p;
-    for (int q = 0; q < 8; ++q) memo.hook[q] = lane::g_last_plan[q];
-    memo.set = true;
-    return p;
+    lane_plan_hook(in, memo.plan, lane::g_last_plan);
+    if (memo.plan.txy) lane::g_last_listed = gs.listed_sink ? *(volatile int *)gs.listed_sink : gs.last_listed; // (the freshest value the device has delivered)
+    return memo.plan;
 }
 
-static LanePlan plan_lane_fresh(const DBox &b, const Grid &g, int64_t N, int64_t M, const GridStats &gs, double rc, bool fcna, bool count)
-{
-    using namespace lane;
-    LanePlan p{};
-    for (int k = 0; k < 8; ++k) g_last_plan[k] = 0;
-    if (N <= 0) { g_last_plan[6] = -1; return p; }
-    if (const int why = lane_refusal(b, g, M)) { g_last_plan[6] = why; return p; }
-    if (!(rc > 1e-12 && rc < 1e12)) { g_last_plan[6] = -4; return p; }
-    int64_t runs = 0, over32 = 0, over96 = 0;
-    for (int k = 1; k < GridStats::NBIN; ++k) runs += gs.v[k];
-    for (int len = 29; len <= 97; ++len) over32 += gs.v[1 + len]; // (a little below the limits: the statistics are the previous call's)
-    for (int len = 89; len <= 97; ++len) over96 += gs.v[1 + len];
-    const bool long_runs = runs > 0 && (double)over32 > 0.002 * (double)runs; // many runs would not fit one 32-bit hit mask: the wide instance (three)
-    // cells so full that more than a few per cent of the runs would not fit three masks (fewer — the wider last cell of a small box — go to the mop-up kernel)
-    if (runs > 0 && (double)over96 > 0.05 * (double)runs) { g_last_plan[6] = -5; g_last_plan[5] = (int)over96; g_last_plan[4] = (int)runs; return p; }
-    const int64_t occ = gs.v[0] > 0 ? gs.v[0] : g.ncell;
-    const double pop = (double)N / (double)occ; // mean atoms per cell of the occupied region
-    // rows of 65 ... 128 slots: measured against the round-1 tiled kernel on 4 M atoms of rattled fcc Cu (tools/rc_sweep.py,
-    // profiles/r04_rc_sweep.txt) — ahead while a cell holds fewer than ~20 atoms (rc 5.6 / 5.8 / 6.0 A: 7.6 -> 5.5, ~8.3 -> 5.9,
-    // 8.8 -> 5.7 ms), behind beyond (rc 6.5 A, 24 atoms per cell: a third of the tiles hold a run of more than 96 candidates and
-    // go to the mop-up code, 10.9 -> 12.7 ms)
-    if (M > 64 && pop > 19.5) { g_last_plan[6] = -7; g_last_plan[5] = (int)(1000.0 * pop); return p; }
-    // rows of at most 16 slots in cells of a few atoms: one-byte tickets, the lean LDS layout, rows written by the centre's lane;
-    // four workgroups per CU where the instance keeps to 128 VGPRs
-    const bool tk8 = (count || M <= 16) && !long_runs;
-    const int max_wgs = tk8 ? 4 : 3;
-    // LDS budget: four workgroups per CU (the 128-VGPR instance only), else three, two, one, if the tile that allows is not
-    // much worse than what fewer would get.  Rows of many slots in cells of many atoms (rc = 5 A, 50 slots: the reference's
-    // own benchmark call) leave few centres per tile: the ticket rows are sized for them (rw rows per wave), not for 64.
-    Shape best{0, 0};
-    int best_cap = 0, best_wgs = 0, best_rw = 64;
-    double best_score = -1.0;
-    const int nthr = NW * 64;
-    for (int wgs = max_wgs; wgs >= 1; --wgs) {
-        // static tables (1.1 KB: the run table, scan scratch, flags) and a margin.  LDS is handed out in 512-byte granules: 40 960 B
-        // in all give four workgroups per CU (measured: 40 544 do, 41 216 do not; 52.9 KB three, 54.3 KB not)
-        const long budget = 160 * 1024 / wgs - 1088 - (wgs == 4 ? 64 : 1600);
-        for (int txy = 1; txy <= 8; ++txy)
-            for (int tz = 1; tz <= 24; ++tz) {
-                const int nh = (txy + 2) * (txy + 2) * (tz + 2);
-                if (nh > nthr)
-                    continue;
-                const int ncc = txy * txy * tz;
-                const double c = ncc * pop;                                 // centre atoms per tile
-                if (c * 1.15 > CEN_CAP)
-                    continue;
-                int rw = 64;
-                if (!tk8) rw = std::min(64, std::max(8, ((int)std::ceil(c * 1.15 / NW) + 3) & ~3)); // (a row is a multiple of eight bytes: any count keeps the waves' blocks aligned)
-                const long fixed = (long)lds_bytes(0, M, tk8, rw, fcna);
-                const int cap = std::min((int)((budget - fixed - 2) / 42), 2040); // (a centre's LDS index takes 11 bits of its table entry)
-                if (cap < 64 || nh * pop > 0.875 * cap) // head-room for density fluctuations; what overflows goes to the slice pass
-                    continue;
-                const double passes = std::ceil(c * 1.15 / (NW * rw)); // (head-room: a second pass for a handful of centres is a waste)
-                const double util = c / (passes * nthr);                   // lane utilisation of the scan
-                const double reuse = (double)ncc / (double)nh;             // centre cells per staged cell
-                const int wpc = wgs * NW;                                  // waves per CU
-                const double score = util * (0.35 + reuse) * (wpc == 16 ? 1.1 : (wpc == 12 ? 1.0 : (wpc == 8 ? 0.85 : (M > 64 ? 0.45 : 0.6))));
-                if (score > best_score) { best_score = score; best = Shape{txy, tz}; best_cap = cap; best_wgs = wgs; best_rw = rw; }
-            }
-    }
-    if (!best.txy) { g_last_plan[6] = -6; return p; }
-    // Decision band of the single-precision scan (file header).  E bounds the staged coordinates (far-atom check of the
-    // kernel), du the error of one staged coordinate: rounding to f32 plus what the double-precision shift can lose;
-    // |d2_f32 - d2| <= (2 du)(2 sqrt(3) |d| + 6 du) + 5 * 2^-24 max(d2, rc^2) for the three subtractions and the FMA chain.
-    const int hmax = std::max(best.txy, best.tz) + 2;
-    double E = ((double)hmax + 1.5) * rc;
-    double big = E;
-    if (b.tri) { // the halo is a parallelepiped: its edges along the cell vectors, coordinates bounded by their sum
-        double ext = 0, span = 0;
-        for (int d = 0; d < 3; ++d) {
-            const double len = std::sqrt(b.h[3 * d] * b.h[3 * d] + b.h[3 * d + 1] * b.h[3 * d + 1] + b.h[3 * d + 2] * b.h[3 * d + 2]);
-            ext += ((double)((d == 2 ? best.tz : best.txy) + 2) + 1.5) * len * rc / b.thick[d]; // a cell is rc / thickness of the vector
-            span += len;
-        }
-        E = ext;
-        big = E + 3.0 * span;
-        for (int d = 0; d < 3; ++d) big += std::fabs(b.o[d]);
-        big *= 4.0; // the wrap and the frame shift go through the fractional coordinates: a few more roundings
-    } else {
-        // (a raw coordinate may be img::MAX_M + 1 box lengths away from the box: the shift L * n loses at most an ulp of THAT)
-        for (int d = 0; d < 3; ++d) big = std::max(big, std::fabs(b.o[d]) + (double)(img::MAX_M + 2) * std::fabs(b.h[d * 4]) + E);
-    }
-    const double du = std::ldexp(E, -24) * 1.01 + std::ldexp(big, -49);
-    const double rcsq = rc * rc;
-    const double tol = 2.0 * (11.0 * du * rc + 12.0 * std::ldexp(rcsq, -24)); // twice the bound: a wider band costs nothing
-    // e = d2 - c in single precision is within tol of the exact value.  c: the largest float <= rc^2 - tol, so that e < 0 is
-    // a hit for sure; W: the smallest float >= (rc^2 - c) + tol, so that e > W is a miss for sure
-    float c = (float)(rcsq - tol);
-    while ((double)c > rcsq - tol) c = std::nextafterf(c, -INFINITY);
-    const double want = (rcsq - (double)c) + tol;
-    float W = (float)want;
-    while ((double)W < want) W = std::nextafterf(W, INFINITY);
-    p.mid = c;
-    p.T = W;
-    p.txy = best.txy;
-    p.tz = best.tz;
-    p.cap = best_cap;
-    p.tk8 = tk8;
-    p.wgs = best_wgs;
-    p.rw = best_rw;
-    p.occupied = occ;
-    p.last_listed = gs.last_listed;
-    p.listed_sink = gs.listed_sink;
-    g_last_listed = gs.listed_sink ? *(volatile int *)gs.listed_sink : gs.last_listed; // (the freshest value the device has delivered)
-    // "full": (nearly) every 4x4x4 block of cells holds atoms — all tiles are launched, no list of live ones is made.  A couple of
-    // per cent of empty blocks (the corner cell of a 100^3-cell fcc box holds no lattice site) cost a workgroup each that finds no
-    // centre and leaves; the list costs three launches
-    p.full = (double)occ >= 0.98 * (double)g.ncell;
-    g_last_plan[0] = p.txy; g_last_plan[1] = p.tz; g_last_plan[2] = p.cap; g_last_plan[3] = (int)lds_bytes(p.cap, M, tk8, p.rw, fcna);
-    g_last_plan[4] = p.full | (p.tk8 ? 2 : 0) | (p.wgs << 2); g_last_plan[5] = (int)(1000.0 * pop); g_last_plan[6] = (int)std::min<int64_t>(occ, 2147483647); g_last_plan[7] = 1;
-    return p;
-}
-
-// rows (RowsRequest, grid.hpp).  COUNT_ONLY: nn and *max_count only; M is then 1
-int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, int64_t N, const DBox &b, double rc,
+// rows (RowsRequest, grid.hpp).  COUNT_ONLY: nn and *max_count only; M is then 1.  Every number of the launches is the plan's or
+// plan_lane_launch's (neighbor_plan.hpp); gs: the statistics the plan was made from (the slice pass follows last_listed)
+int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, const GridStats &gs, int64_t N, const DBox &b, double rc,
                          const RowsRequest &rows, TileFilter &tf)
 {
     using namespace lane;
     const bool count = rows.pads == RowsRequest::COUNT_ONLY, fill_pads = rows.pads == RowsRequest::WRITE_PADS;
     int *const verlet = rows.verlet, *const nn = rows.nn, *const max_count = rows.max_count, *const pattern = count ? nullptr : rows.pattern;
     double *const dist = rows.dist; const int64_t M = count ? 1 : rows.M;
-    int nt[3];
-    for (int d = 0; d < 3; ++d) {
-        const int T = d == 2 ? plan.tz : plan.txy;
-        nt[d] = (cg.g.nc[d] + T - 1) / T;
-    }
-    const int64_t ntiles = (int64_t)nt[0] * nt[1] * nt[2];
+    const LaneLaunch ll = plan_lane_launch(plan, cg.g.nc, cg.win_lo, cg.win_hi, cg.cen_lo, cg.cen_hi, gs.last_listed);
+    const int *const nt = ll.nt;
+    const int64_t ntiles = ll.ntiles;
     const Shape ts = make_shape(plan.txy, plan.tz, nt[1], nt[2]);
-    const int nsub = ts.tz; // second pass: one-cell slices along z
     unsigned *live = sc.alloc_n<unsigned>((size_t)ntiles);
     int *slot = sc.alloc_n<int>((size_t)ntiles + 1);
     int *tile_list = sc.alloc_n<int>((size_t)ntiles);
     int *flagged = sc.alloc_n<int>((size_t)ntiles);                   // tiles of the first pass for the second (each listed at most once)
-    int *flagged2 = sc.alloc_n<int>((size_t)ntiles * (size_t)nsub);   // slices of the second pass for the thread-per-atom code
+    int *flagged2 = sc.alloc_n<int>((size_t)ntiles * (size_t)ll.nsub); // slices of the second pass for the thread-per-atom code
     if (sc.failed())
         return sc.error();
     hipStream_t st = sc.stream();
-    int per = (int)((ntiles + 7) / 8);
-    int list_mode = 0, tile_base = 0, nt0_run = nt[0];
-    if (plan.full) { // the statistics say that no 4x4x4 block of cells is empty: all tiles are live, workgroup b owns tile b
-        tile_list = nullptr;
-    } else if (cg.win_hi > cg.win_lo) {
-        // the caller promised a window of planes along axis 0 (a slab of a decomposed system, mdh_hint_cell_window) and the cell
-        // grid was built over it: the tiles that can hold atoms are ONE range of tile numbers (axis 0 is the slowest index) —
-        // no list, no pass over the tiles of the global grid to make one
-        tile_list = nullptr;
-        // (tiles of the planes that hold atoms wanting rows: the window, or the centre window inside it)
-        const int w_lo = cg.cen_hi > cg.cen_lo ? std::max(cg.win_lo, cg.cen_lo) : cg.win_lo, w_hi = cg.cen_hi > cg.cen_lo ? std::min(cg.win_hi, cg.cen_hi) : cg.win_hi;
-        const int t_lo = w_lo / ts.txy, t_hi = (std::max(w_hi, w_lo + 1) - 1) / ts.txy;
-        tile_base = t_lo * nt[1] * nt[2];
-        nt0_run = t_hi - t_lo + 1;
-        per = (int)(((int64_t)nt0_run * nt[1] * nt[2] + 7) / 8);
-    } else {
+    if (ll.tiles == LaneLaunch::LIST) {
         hipLaunchKernelGGL(k_tile_live, dim3(grid_for(ntiles, 256)), dim3(256), 0, st, cg.cell_start, cg.g, nt[0], nt[1], nt[2], ts, live, cg.slot_cap);
         MDH_TRY(exclusive_scan_u32(sc, live, slot, ntiles)); // slot[ntiles] = number of live tiles
         hipLaunchKernelGGL(k_tile_compact, dim3(grid_for(ntiles, 256)), dim3(256), 0, st, live, slot, (int)ntiles, tile_list);
-        // live tiles expected from the last known occupancy (+25 %); a workgroup takes further tiles of its chunk if that was too few
-        const int64_t est_live = std::max<int64_t>(1, plan.occupied / std::max(1, ts.txy * ts.txy * ts.tz) * 2);
-        per = std::max(1, std::min(per, (int)((est_live + est_live / 4 + 7) / 8)));
-        list_mode = 1;
+    } else {
+        tile_list = nullptr;
     }
-    const dim3 grid((unsigned)(per * 8));
-    const size_t lds = lds_bytes(plan.cap, count ? 1 : M, plan.tk8, plan.rw, pattern != nullptr);
-    const int cen_lo = cg.cen_hi > cg.cen_lo ? cg.cen_lo : 0, cen_hi = cg.cen_hi > cg.cen_lo ? cg.cen_hi : 0x7fffffff;
+    const dim3 grid(ll.grid);
+    const size_t lds = (size_t)plan.lds_bytes;
     const int Mi = (int)M, wp = fill_pads ? (rows.ids_only ? 3 : 1) : 0; // bit 1: the wide instance neither computes nor stores the distances (RowsRequest::ids_only)
     const float negc = -plan.mid;
-    const int nt2b = nt[2] * nsub;
-    // second pass: workgroups walk the listed tiles' slices.  Nothing was listed by the previous build with this (N, grid)
-    // (a lattice, nearly always): no slice pass at all — the mop-up takes the first pass's own list, whatever turns up on it
-    // this time, slowly but correctly, and reports its length so that the next build launches the slice pass again (a
-    // stand-by launch that finds an empty list is 5 us and a kernel boundary of every build)
-    const bool slice_pass = plan.last_listed != 0;
-    const dim3 grid2(1024u);
-    const Shape ts2 = make_shape(ts.txy, 1, nt[1], nt2b);
+    const dim3 grid2(SLICE_GRID);
+    const Shape ts2 = make_shape(ts.txy, 1, nt[1], ll.nt2b);
     const bool indirect = !cg.pk; // CellGrid::ix
     const lane::IndirectSrc isrc{cg.ix, cg.iy, cg.iz, cg.imv, cg.order};
     const int slot_hi = cg.slot_cap ? (int)(cg.slot_hi - 4) : 0; // a slot grid: id k >= 4 of cell c at 4 c + k + slot_hi (slot_pos); 0: compact
@@ -1530,8 +1365,8 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
         if (lds > 60 * 1024) /* above the default dynamic-LDS limit: raise it for the instance about to run */                            \
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND, SLOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((k_neighbor_lane<COUNT, TRI, LOOP, FCNA, TK8, IND, SLOT>), GRID, dim3(NW * 64), lds, st, cg.pk, cg.cell_start, b, \
-                           cg.g, rc, negc, plan.T, verlet, dist, nn, Mi, wp, plan.cap, cg.flags, nullptr, __VA_ARGS__, pattern, tf.cna_todo, JT0, plan.rw, tile_base, plan.listed_sink, \
-                           cen_lo, cen_hi, isrc, slot_hi); \
+                           cg.g, rc, negc, plan.T, verlet, dist, nn, Mi, wp, plan.cap, cg.flags, nullptr, __VA_ARGS__, pattern, tf.cna_todo, JT0, plan.rw, ll.tile_base, gs.listed_sink, \
+                           ll.cen_lo, ll.cen_hi, isrc, slot_hi); \
     } while (0)
 #define MDH_LANE_PASS(COUNT, TRI, LOOP, FCNA, TK8, GRID, JT0, ...)                                                                        \
     do {                                                                                                                                  \
@@ -1544,15 +1379,15 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
     // otherwise); second pass: one-cell slices of what the first listed
 #define MDH_LANE_LAUNCH(COUNT, TRI, FCNA, TK8)                                                                                            \
     do {                                                                                                                                  \
-        if (list_mode) {                                                                                                                  \
+        if (ll.tiles == LaneLaunch::LIST) {                                                                                               \
             MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, grid, 0, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
-            if ((int64_t)per * 8 < ntiles)                                                                                                \
-                MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, dim3(512), per, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
+            if (ll.standby)                                                                                                               \
+                MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, dim3(STANDBY_GRID), ll.per, nt[0], nt[1], nt[2], ts, tile_list, slot + ntiles, 1, max_count, flagged, nullptr, 0, 1, 2); \
         } else {                                                                                                                          \
-            MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, grid, 0, nt0_run, nt[1], nt[2], ts, nullptr, slot + ntiles, 0, max_count, flagged, nullptr, 0, 1, 2); \
+            MDH_LANE_PASS(COUNT, TRI, false, FCNA, TK8, grid, 0, ll.nt0_run, nt[1], nt[2], ts, nullptr, slot + ntiles, 0, max_count, flagged, nullptr, 0, 1, 2); \
         }                                                                                                                                 \
-        if (slice_pass)                                                                                                                   \
-            MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, grid2, 0, nt[0], nt[1], nt2b, ts2, nullptr, cg.flags + 2, 1, max_count, flagged2, flagged, nt[2], nsub, 3); \
+        if (ll.slice_pass)                                                                                                                \
+            MDH_LANE_PASS(COUNT, TRI, true, FCNA, TK8, grid2, 0, nt[0], nt[1], ll.nt2b, ts2, nullptr, cg.flags + 2, 1, max_count, flagged2, flagged, nt[2], ll.nsub, 3); \
     } while (0)
     if (count) {
         if (plan.tk8) { if (b.tri) MDH_LANE_LAUNCH(true, true, false, true); else MDH_LANE_LAUNCH(true, false, false, true); }
@@ -1571,14 +1406,14 @@ int launch_neighbor_lane(Scope &sc, const CellGrid &cg, const LanePlan &plan, in
     // what the passes listed for the thread-per-atom code (k_neighbor_mop): the slices of the second pass, or, without one, the
     // tiles of the first in its own tiling
     tf.flag = reinterpret_cast<const unsigned char *>(flagged2); // (non-null: "a tiled kernel ran"; the per-tile byte flags are not used with a list)
-    tf.any = cg.flags + (slice_pass ? 3 : 2);
+    tf.any = cg.flags + (ll.slice_pass ? 3 : 2);
     tf.moved = cg.flags;
-    tf.list = slice_pass ? flagged2 : flagged;
-    tf.list_cap = (int)std::min<int64_t>(slice_pass ? ntiles * nsub : ntiles, 2147483647);
+    tf.list = ll.slice_pass ? flagged2 : flagged;
+    tf.list_cap = ll.list_cap;
     tf.tile = ts.txy;
-    tf.tile_z = slice_pass ? ts2.tz : ts.tz;
-    tf.nt[0] = nt[0]; tf.nt[1] = nt[1]; tf.nt[2] = slice_pass ? nt2b : nt[2];
-    tf.listed_sink = slice_pass ? nullptr : plan.listed_sink; // (the slice pass reports the first pass's count itself)
+    tf.tile_z = ll.mop_tile_z;
+    tf.nt[0] = nt[0]; tf.nt[1] = nt[1]; tf.nt[2] = ll.mop_nt2;
+    tf.listed_sink = ll.slice_pass ? nullptr : gs.listed_sink; // (the slice pass reports the first pass's count itself)
     return MDH_OK;
 }
 
@@ -1597,6 +1432,40 @@ extern "C" int mdh_debug_neighbor_plan(int *plan8)
     for (int k = 0; k < 8; ++k) plan8[k] = mdh::lane::g_last_plan[k];
     if (plan8[0] > 0 && mdh::last_grid_was_slot()) plan8[4] |= 256; // bit 8 of [4]: the last neighbor build's cell grid was a slot grid (CellGrid::slot_cap)
     mdh::lane::g_last_plan[7] = 0; // [7] = 1: the plan was made since the last query
+    return MDH_OK;
+}
+// the planners of neighbor_plan.hpp on plain values (include/mdapy_amd.h has the layout); no device is touched
+extern "C" int mdh_debug_lane_plan(const int64_t *in_i, const double *in_d, const int *stats, double *out)
+{
+    using namespace mdh;
+    LanePlanIn in{};
+    TiledPlanIn ti{};
+    for (int d = 0; d < 3; ++d) { in.nc[d] = ti.nc[d] = (int)in_i[d]; in.pbc[d] = ti.pbc[d] = (int)in_i[5 + d]; in.o[d] = in_d[9 + d]; in.thick[d] = in_d[12 + d]; }
+    for (int d = 0; d < 9; ++d) in.h[d] = in_d[d];
+    in.ncell = ti.ncell = in_i[3]; in.mode = ti.mode = (int)in_i[4]; in.tri = ti.tri = (int)in_i[8];
+    in.N = ti.N = in_i[9]; in.M = ti.M = in_i[10]; in.fcna = in_i[11] != 0; in.count = in_i[12] != 0; in.rc = in_d[15];
+    GridStats gs;
+    for (int k = 0; k < GridStats::NBIN; ++k) in.v[k] = gs.v[k] = stats[k];
+    gs.last_listed = (int)in_i[17];
+    ti.occupied_cells = stats[0];
+    const LanePlan p = in_i[18] ? plan_lane_memo(in, gs) : plan_lane(in);
+    int hook[8];
+    lane_plan_hook(in, p, hook);
+    for (int k = 0; k < 46; ++k) out[k] = 0.0;
+    const double lane[15] = {(double)p.txy, (double)p.tz, (double)p.cap, (double)p.tk8, (double)p.wgs, (double)p.rw, (double)p.mid, (double)p.T, (double)p.full,
+                             (double)p.occupied, (double)p.reason, (double)p.lds_bytes, (double)p.pop, (double)p.over96, (double)p.runs};
+    std::copy(lane, lane + 15, out);
+    std::copy(hook, hook + 8, out + 15);
+    if (p.txy) {
+        const LaneLaunch ll = plan_lane_launch(p, in.nc, (int)in_i[13], (int)in_i[14], (int)in_i[15], (int)in_i[16], gs.last_listed);
+        const double launch[16] = {(double)ll.nt[0], (double)ll.nt[1], (double)ll.nt[2], (double)ll.ntiles, (double)ll.tiles, (double)ll.tile_base, (double)ll.nt0_run,
+                                   (double)ll.per, (double)ll.grid, (double)ll.standby, (double)ll.slice_pass, (double)ll.nsub, (double)ll.nt2b, (double)ll.list_cap,
+                                   (double)ll.mop_tile_z, (double)ll.mop_nt2};
+        std::copy(launch, launch + 16, out + 23);
+        out[44] = ll.cen_lo; out[45] = ll.cen_hi;
+    }
+    const TiledPlan tp = plan_tiled(ti);
+    out[39] = tp.tile; out[40] = tp.tile_z; out[41] = tp.cellshift; out[42] = tp.full; out[43] = (double)tp.occupied;
     return MDH_OK;
 }
 extern "C" int mdh_debug_run_offset_table(int txy, int tz, unsigned *out3)

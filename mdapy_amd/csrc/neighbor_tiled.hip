@@ -42,21 +42,9 @@
 
 namespace mdh {
 
-#ifndef MDH_HALO_CAP
-#define MDH_HALO_CAP 1024
-#endif
-static constexpr int HALO_CAP = MDH_HALO_CAP; // atoms a tile's halo may hold in LDS (30 B each)
-static constexpr int NT = 256;        // threads per workgroup
-#ifndef MDH_MAX_NH
-#define MDH_MAX_NH 512
-#endif
-static constexpr int MAX_NH = MDH_MAX_NH;    // halo cells a tile may have
-static constexpr int MAX_COLS = 64;   // (x,y) columns of centre cells a tile may have
-static constexpr int TICK_STRIDE = NT + 2; // ticket slot stride (u16 units): 516 B -> consecutive slots shift by one bank
+// HALO_CAP, NT, MAX_NH, MAX_COLS, TICK_STRIDE (namespace tiled) and TileShape: neighbor_plan.hpp, shared with the planner (plan_tiled, plan_tiled_launch)
+using namespace tiled;
 static constexpr int NEUTRAL = img::CELL_NEUTRAL; // a halo cell's image code "no shift" (grid.hpp img::)
-
-// Tile shape (cells): TXY x TXY x TZ
-struct TileShape { int txy, tz; };
 
 __device__ __forceinline__ int excl_scan_block(int v, int *scratch, int *total)
 {
@@ -393,79 +381,17 @@ __global__ __launch_bounds__(256) void k_tile_compact(const unsigned *__restrict
     if (t < ntiles && live[t]) tile_list[slot[t]] = t;
 }
 
-static size_t tiled_lds_bytes(int64_t M)
-{
-    return (size_t)HALO_CAP * (24 + 4 + 2) + (size_t)NT * (24 + 4 + 4) + (size_t)TICK_STRIDE * (size_t)M * 2;
-}
-
-// pick the tile shape for a mean cell population `pop`
-static TileShape choose_shape(double pop)
-{
-    TileShape best{0, 0};
-    double best_score = -1.0;
-    for (int txy = 2; txy <= 8; ++txy)
-        for (int tz = 2; tz <= 16; ++tz) {
-            const int nh = (txy + 2) * (txy + 2) * (tz + 2);
-            if (nh > MAX_NH || txy * txy > MAX_COLS)
-                continue;
-            if (nh * pop > 0.86 * HALO_CAP) // head-room for density fluctuations; overflowing tiles fall back
-                continue;
-            const double c = txy * txy * tz * pop;                       // centre atoms per tile
-            const double util = c / (std::ceil(c / NT) * NT);           // lane utilisation of the scan
-            const double reuse = (double)(txy * txy * tz) / (double)nh; // centre cells per staged cell
-            const double score = util * (0.35 + reuse);
-            if (score > best_score) { best_score = score; best = TileShape{txy, tz}; }
-        }
-    return best;
-}
-
-// How many cells hold atoms?  The tile shape is sized for the population of the OCCUPIED region: a box that is mostly empty
-// (vacuum around a slab or a particle, the other ranks' slabs of a decomposed system) would otherwise get tiles whose halo
-// overflows LDS wherever the atoms are.  occupied_cells is GridStats::v[0] of the signature (grid_stats_hint, neighbor_lane.hip:
-// counted on the device in blocks of 4 x 4 x 4 cells, read by the next call).  A stale value costs speed, never correctness
-// (overflowing tiles fall back to the thread-per-atom kernel).
-TiledPlan plan_tiled(const DBox &b, const Grid &g, int64_t N, int64_t M, int64_t occupied_cells)
-{
-    TiledPlan p{0, 0, false, false, 0};
-    if (b.tri || g.mode != 0 || N <= 0 || M <= 0)
-        return p;
-    const double pop = (double)N / (double)(occupied_cells > 0 ? occupied_cells : g.ncell); // mean atoms per occupied cell
-    const TileShape sh = choose_shape(pop);
-    if (!sh.txy)
-        return p;
-    if (tiled_lds_bytes(M) > 62 * 1024) // ticket rows must fit next to the halo (<= 64 KiB: two workgroups per CU)
-        return p;
-    int mp = 1;
-    while (mp < M) mp <<= 1;
-    if (mp > NT)
-        return p;
-    p.tile = sh.txy;
-    p.tile_z = sh.tz;
-    p.full = occupied_cells >= g.ncell;
-    p.occupied = occupied_cells > 0 ? occupied_cells : g.ncell;
-    p.cellshift = true;
-    for (int d = 0; d < 3; ++d)
-        if (b.pbc[d] && g.nc[d] < 7)
-            p.cellshift = false;
-    return p;
-}
-
+// per: workgroups per XCD chunk; list: the instance whose workgroups walk a list of tiles, looping over further ones of their chunk
+// (false: a full box, one tile per workgroup: the straight-line kernel)
 template <bool CS>
 static void launch_one(hipStream_t st, const CellGrid &cg, const DBox &b, double rc, int *verlet, double *dist, int *nn,
-                       int M, bool fill_pads, unsigned char *tile_flag, const int *nt, int want_moved, TileShape ts,
-                       const int *tile_list, const int *n_live, int64_t est_live, bool standby)
+                       int M, bool fill_pads, unsigned char *tile_flag, const TiledLaunch &tl, int want_moved, TileShape ts,
+                       const int *tile_list, const int *n_live, int per, bool list)
 {
-    const int ntiles = nt[0] * nt[1] * nt[2];
-    int per = (ntiles + 7) / 8;
-    if (est_live > 0) // tiles expected to hold atoms (+25 %); more than that and workgroups loop (k_neighbor_tiled)
-        per = std::max(1, std::min(per, (int)((est_live + est_live / 4 + 7) / 8)));
-    if (standby) // the variant that the device flag will most likely send home: three workgroups per CU, looping if it does run
-        per = std::min(per, 96);
+    const int *nt = tl.nt;
+    const int mp_shift = tl.mp_shift;
+    const size_t lds = tl.lds;
     dim3 grid((unsigned)(per * 8)), block(NT);
-    const size_t lds = tiled_lds_bytes(M);
-    int mp_shift = 0;
-    while ((1 << mp_shift) < M) ++mp_shift;
-    const bool list = tile_list != nullptr || standby || per * 8 < ntiles; // full box, one tile per workgroup: the straight-line kernel
     if (fill_pads) {
         if (list) hipLaunchKernelGGL((k_neighbor_tiled<CS, 2, true>), grid, block, lds, st, cg.xs, cg.ys, cg.zs, cg.order, cg.mvs, cg.cell_start, b, cg.g, rc, verlet, dist, nn, M, mp_shift, cg.flags, tile_flag, nt[0], nt[1], nt[2], want_moved, ts, tile_list, n_live);
         else hipLaunchKernelGGL((k_neighbor_tiled<CS, 2, false>), grid, block, lds, st, cg.xs, cg.ys, cg.zs, cg.order, cg.mvs, cg.cell_start, b, cg.g, rc, verlet, dist, nn, M, mp_shift, cg.flags, tile_flag, nt[0], nt[1], nt[2], want_moved, ts, tile_list, n_live);
@@ -475,17 +401,15 @@ static void launch_one(hipStream_t st, const CellGrid &cg, const DBox &b, double
     }
 }
 
+// every number of the launches is the plan's or plan_tiled_launch's (neighbor_plan.hpp)
 int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, int64_t N, const DBox &b, double rc,
                           const RowsRequest &rows, TileFilter &tf)
 {
     const bool fill_pads = rows.pads == RowsRequest::WRITE_PADS;
     const TileShape ts{plan.tile, plan.tile_z};
-    int nt[3];
-    for (int d = 0; d < 3; ++d) {
-        const int T = d == 2 ? ts.tz : ts.txy;
-        nt[d] = (cg.g.nc[d] + T - 1) / T;
-    }
-    const int64_t ntiles = (int64_t)nt[0] * nt[1] * nt[2];
+    const TiledLaunch tl = plan_tiled_launch(plan, cg.g.nc, rows.M);
+    const int *nt = tl.nt;
+    const int64_t ntiles = tl.ntiles;
     unsigned char *tile_flag = sc.alloc_n<unsigned char>((size_t)ntiles);
     if (sc.failed())
         return sc.error();
@@ -496,10 +420,7 @@ int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, 
         return sc.error();
     hipStream_t st = sc.stream();
     MDH_HIP(hipMemsetAsync(tile_flag, 0, (size_t)ntiles, st));
-    // live tiles expected from the last known occupancy: occupied cells / cells per tile (tiles are cut partly empty at the
-    // surface of the occupied region, hence the head-room in launch_one)
-    const int64_t est_live = plan.full ? 0 : std::max<int64_t>(1, plan.occupied / std::max(1, ts.txy * ts.txy * ts.tz) * 2);
-    if (plan.full) { // the occupancy count says that no 4x4x4 block of cells is empty: all tiles are live, no list needed
+    if (!tl.listed) { // the occupancy count says that no 4x4x4 block of cells is empty: all tiles are live, no list needed
         tile_list = nullptr;
     } else {
         hipLaunchKernelGGL(k_tile_live, dim3(grid_for(ntiles, 256)), dim3(256), 0, st, cg.cell_start, cg.g, nt[0], nt[1], nt[2], ts, live);
@@ -508,8 +429,9 @@ int launch_neighbor_tiled(Scope &sc, const CellGrid &cg, const TiledPlan &plan, 
     }
     // Two launches, one of which returns at once on the device flag: image numbers from the cell / atom codes when
     // the binning pass found them valid (and the grid allows it), the exact threshold search otherwise.
-    if (plan.cellshift) launch_one<true>(st, cg, b, rc, rows.verlet, rows.dist, rows.nn, (int)rows.M, fill_pads, tile_flag, nt, 0, ts, tile_list, slot + ntiles, est_live, false);
-    launch_one<false>(st, cg, b, rc, rows.verlet, rows.dist, rows.nn, (int)rows.M, fill_pads, tile_flag, nt, plan.cellshift ? 1 : -1, ts, tile_list, slot + ntiles, est_live, plan.cellshift);
+    if (plan.cellshift) launch_one<true>(st, cg, b, rc, rows.verlet, rows.dist, rows.nn, (int)rows.M, fill_pads, tile_flag, tl, 0, ts, tile_list, slot + ntiles, tl.per, tl.listed);
+    launch_one<false>(st, cg, b, rc, rows.verlet, rows.dist, rows.nn, (int)rows.M, fill_pads, tile_flag, tl, plan.cellshift ? 1 : -1, ts, tile_list, slot + ntiles,
+                      plan.cellshift ? tl.per_standby : tl.per, plan.cellshift || tl.listed); // (behind the first it only stands by)
     MDH_HIP(hipGetLastError());
     tf.flag = tile_flag;
     tf.any = cg.flags + 2;
