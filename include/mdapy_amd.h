@@ -230,6 +230,22 @@ int mdh_parse_table(const char *text, int64_t nbytes, int text_space, int64_t nr
  * (high, low word); the field converter itself: 0 converted, 1 undecided (host must redo), 2 not a number */
 int mdh_debug_text_pow5(int q, uint64_t *out2);
 int mdh_debug_parse_double(const char *s, int64_t len, double *out);
+/*
+ * replaces the section search of BuildSystem.read_data  src/mdapy/load_save.py:1064-1092 (every line stripped and split, the
+ * first line whose first token is a section word starts that section).  One pass over `text` (nbytes, in host memory or HBM:
+ * text_space) looks at every line start — byte 0 and one past every '\n' —, skips blanks, tabs and '\r' and compares the token
+ * there (it ends at a blank, tab, '\r', '\n' or the end of the text) with words[0 .. nwords) (host, C strings: 1..32 words
+ * of 1..15 bytes, distinct).  first_offset[k] (host) = byte offset of the first LINE whose first token is words[k], -1 when
+ * there is none; *line_count (host) = lines of the text (newlines, + 1 when it does not end with one).  The offsets are kept
+ * with a 64-bit atomic minimum: the result does not depend on execution order.  MDH_ERR_ARG before any device work: null
+ * pointers, nbytes < 0, a bad table of words.  Synchronises `stream`.
+ */
+int mdh_scan_sections(const char *text, int64_t nbytes, int text_space, const char *const *words, int nwords, int64_t *first_offset,
+                      int64_t *line_count, void *stream);
+/* test hook (runs on the host, no GPU needed): the same result from a loop over the line starts with the kernel's own token
+ * matcher (csrc/text_sections.hpp); `text` in host memory */
+int mdh_debug_scan_sections(const char *text, int64_t nbytes, const char *const *words, int nwords, int64_t *first_offset,
+                            int64_t *line_count);
 /* The inverse (csrc/text_format.hip): nrows x ncol numeric columns -> the bytes of a text table, fields joined by one blank,
  * rows ended by "\n"; floats as Python's format(v, ".10f") (exact, round-half-to-even; "NaN", "inf", "-inf" for the
  * non-finite), integers in plain decimal.  kinds[c] (host): 0 f64, 1 f32, 2 i32, 3 i64, 4 coded string — an i32 column of
@@ -381,6 +397,15 @@ int mdh_spatial_sort(const double *x, const double *y, const double *z, int64_t 
                      const int *boundary3, double *xs, double *ys, double *zs, int *perm, int64_t *n_sorted, int space, void *stream);
 /* mdh_permute: out[p] = in[perm[p]] (scatter == 0) or out[perm[p]] = in[p] (scatter != 0) for N elements of 4 or 8 bytes. */
 int mdh_permute(const void *in, const int *perm, int64_t N, int elem_bytes, int scatter, void *out, int space, void *stream);
+/* mdh_match_ids: two tables keyed by atom id — replaces the dict join of BuildSystem.read_data, src/mdapy/load_save.py:1295-1297
+ * (Velocities rows looked up by the ids of the Atoms rows).  want, have (N) i32; row_of[i] (N) i32 = the LARGEST r with
+ * have[r] == want[i] (of two rows with one id the last wins, as in a dict), -1 when there is none.  status4 (host): [0] the i
+ * without a row, [1] the smallest of them (-1: none), [2] the i with row_of[i] != i (0: the tables are in one order, nothing
+ * needs to move), [3] 1 when max(have) - min(have) >= 4 N: the ids are too sparse for a table of rows indexed by id, NOTHING was
+ * computed and the caller has to sort (mdapy_amd/_order.py does, with the same result).  Otherwise the table is filled with an
+ * atomic maximum of the row index: the result does not depend on execution order.  MDH_ERR_ARG before any device work: null
+ * pointers, N outside 0 .. 2^31 - 2.  Synchronises `stream`. */
+int mdh_match_ids(const int *want, const int *have, int64_t N, int *row_of, int64_t *status4, int space, void *stream);
 /* xs[p] = x[perm[p]] (and y, z): the three position columns through one permutation in one pass — the next frame of a trajectory read
  * through the previous frame's cell order (System's twin; no reference counterpart, see mdh_spatial_sort).  perm must hold indices in [0, N). */
 int mdh_gather_positions(const double *x, const double *y, const double *z, const int *perm, int64_t N, double *xs, double *ys, double *zs,

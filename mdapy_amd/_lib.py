@@ -59,6 +59,8 @@ _SIGNATURES = {
     "mdh_parse_table": [vp, i64, cint, i64, cint, vp, vp, vp, i64, vp, cint, vp],
     "mdh_debug_text_pow5": [cint, vp],
     "mdh_debug_parse_double": [C.c_char_p, i64, vp],
+    "mdh_scan_sections": [vp, i64, cint, vp, cint, vp, vp, vp],
+    "mdh_debug_scan_sections": [vp, i64, vp, cint, vp, vp],
     "mdh_format_table": [i64, cint, vp, vp, vp, vp, vp, vp, i64, vp, vp, cint, vp],
     "mdh_shift_rotate": [vp, vp, vp, i64, vp, vp, vp, vp, vp, cint, vp],
     "mdh_debug_format_double": [dbl, vp],
@@ -76,6 +78,7 @@ _SIGNATURES = {
     "mdh_order_statistic": [vp, vp, vp, i64, vp, vp, vp, vp, cint, vp],
     "mdh_spatial_sort": [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, cint, vp],
     "mdh_permute": [vp, vp, i64, cint, cint, vp, cint, vp],
+    "mdh_match_ids": [vp, vp, i64, vp, vp, cint, vp],
     "mdh_gather_positions": [vp, vp, vp, vp, i64, vp, vp, vp, cint, vp],
     "mdh_translate_rows": [vp, vp, vp, vp, i64, i64, vp, vp, vp, cint, vp],
     "mdh_slab_append_ghosts_static": [vp, vp, i64, vp, cint, vp, i64, vp],

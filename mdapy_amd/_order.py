@@ -52,6 +52,38 @@ def permute(values, perm, scatter=False):
     return out
 
 
+def match_ids(want, have):
+    """two tables keyed by id (mdh_match_ids): -> (row_of, misses, first_missing, moved).  row_of[i] i32 = the largest r with
+    have[r] == want[i] or -1, ``misses`` the number of -1, ``first_missing`` the smallest such i (-1: none), ``moved`` the
+    number of i with row_of[i] != i (0: the two tables are in one order).  Ids too sparse for the library's table of rows
+    (max - min >= 4 N) are sorted instead (torch: plumbing) — the same result."""
+    N = int(len(want))
+    if int(len(have)) != N:
+        raise ValueError(f"match_ids: {N} ids wanted, {int(len(have))} rows to choose from")
+    on_dev = not (isinstance(want, np.ndarray) and isinstance(have, np.ndarray))
+    row_of = HArray.empty((N,), i32) if on_dev else np.empty(N, i32)
+    status = np.zeros(4, dtype=np.int64)
+    c = Call(want, have, row_of)
+    pw, ph = c.inp(want, i32), c.inp(have, i32)
+    c.done(_lib.lib().mdh_match_ids(pw, ph, N, c.out(row_of, i32, upload=False), status.ctypes.data, c.space, c.stream))
+    if not status[3]:
+        return row_of, int(status[0]), int(status[1]), int(status[2])
+    from .devarray import torch
+
+    t = torch()
+    w = want.dev() if isinstance(want, HArray) else t.from_numpy(np.ascontiguousarray(want, dtype=i32)).cuda()
+    h = have.dev() if isinstance(have, HArray) else t.from_numpy(np.ascontiguousarray(have, dtype=i32)).cuda()
+    keys, rows = t.sort(h, stable=True)  # (stable: of equal ids the last row comes last)
+    at = t.searchsorted(keys, w, right=True) - 1  # the last key <= want[i]
+    hit = (at >= 0) & (keys[at.clamp(min=0)] == w)
+    rows_of = t.where(hit, rows[at.clamp(min=0)], t.full_like(at, -1)).to(t.int32)
+    miss = t.nonzero(~hit).flatten()
+    misses = int(miss.numel())
+    first = int(miss[0]) if misses else -1
+    moved = int((rows_of != t.arange(N, dtype=t.int32, device=rows_of.device)).sum())
+    return (HArray(rows_of) if on_dev else rows_of.cpu().numpy()), misses, first, moved
+
+
 def gather_positions(x, y, z, perm):
     """(x[perm], y[perm], z[perm]) in one pass (mdh_gather_positions)"""
     N = int(len(x))

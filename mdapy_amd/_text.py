@@ -3,6 +3,7 @@
 Two pieces: :func:`stream_to_device` moves a file's bytes into HBM through two pinned buffers (the next chunk is read from
 the file while the previous one crosses PCIe), :func:`parse_table` runs ``mdh_parse_table`` on the resident text and
 patches the few fields the device hands back (``float()`` / ``int()`` on the host — the reference's own conversion).
+:func:`scan_sections` finds the section lines of a LAMMPS data file in the resident text (``mdh_scan_sections``).
 
 And of its inverse, the formatter (csrc/text_format.hip): typed columns in HBM -> the bytes of a text table.
 :func:`format_table` / :func:`format_chunks` run ``mdh_format_table`` (the whole table, or pieces of rows made on demand),
@@ -124,6 +125,28 @@ def parse_table(text, nrows, kinds, redo_cap=1 << 16):
             dev[t.as_tensor(rows, dtype=t.int64, device=dev.device)] = t.as_tensor(vals_of[c], dtype=dev.dtype, device=dev.device)
     out = [_unpack_strings(col, long_strings.get(c)) if k == STR else col for c, (k, col) in enumerate(zip(kinds, cols))]
     return out, lines
+
+
+def _word_table(words):
+    raw = [str(w).encode() for w in words]
+    return (ctypes.c_char_p * len(raw))(*raw), len(raw)
+
+
+def scan_sections(text, words):
+    """``text``: uint8 tensor in HBM (mdh_scan_sections) or ``bytes`` (the host twin of the scan, mdh_debug_scan_sections — no
+    device needed).  Returns ({word: byte offset of the first line whose first token is that word}, lines of the text); a word
+    that starts no line is left out."""
+    table, n = _word_table(words)
+    first = np.full(max(n, 1), -1, dtype=np.int64)
+    lines = ctypes.c_int64(0)
+    if isinstance(text, (bytes, bytearray, memoryview)):
+        raw = bytes(text)
+        rc = _lib.lib().mdh_debug_scan_sections(raw, len(raw), table, n, first.ctypes.data, ctypes.addressof(lines))
+    else:
+        rc = _lib.lib().mdh_scan_sections(int(text.data_ptr()), int(text.numel()), _lib.DEVICE, table, n, first.ctypes.data,
+                                          ctypes.addressof(lines), current_stream_ptr())
+    _lib.check(rc)
+    return {str(w): int(o) for w, o in zip(words, first) if o >= 0}, int(lines.value)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

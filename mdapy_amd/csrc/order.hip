@@ -142,6 +142,68 @@ __global__ __launch_bounds__(256) void k_translate_rows(const int *__restrict__ 
     }
 }
 
+// ---- two tables keyed by atom id (the Atoms and Velocities sections of a LAMMPS data file, src/mdapy/load_save.py:1295-1297: a dict
+// from the second table's ids to its rows, looked up with the first table's ids — the last of two rows with one id wins, an id
+// without a row is a KeyError).  Ids of a span below 4 N index a table of rows directly.
+// (grids of at most IDS_BLOCKS workgroups that stride over the rows: a workgroup's atomics on the result words come once, at its
+// end — one word takes ~90 atomics per microsecond, and a workgroup per 256 of 10 M rows would queue 39 000 on each)
+constexpr int IDS_BLOCKS = 2048;
+__global__ __launch_bounds__(256) void k_ids_range(const int *__restrict__ have, int64_t N, int *__restrict__ lohi)
+{
+    __shared__ int s_lo[4], s_hi[4];
+    int lo = 2147483647, hi = -2147483647 - 1;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < N; r += (int64_t)gridDim.x * blockDim.x) {
+        const int v = have[r];
+        lo = min(lo, v);
+        hi = max(hi, v);
+    }
+    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicMin(&lohi[0], min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])));
+        atomicMax(&lohi[1], max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
+    }
+}
+
+// table[id - lo] = the largest row that carries id (an atomic maximum: last wins, in whatever order the rows arrive)
+__global__ __launch_bounds__(256) void k_ids_fill(const int *__restrict__ have, int64_t N, int lo, int64_t span, int *__restrict__ table)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N)
+        return;
+    const int64_t d = (int64_t)have[r] - lo;
+    if (d >= 0 && d < span) atomicMax(&table[d], (int)r);
+}
+
+// row_of[i] = table[want[i] - lo] or -1; out[0] misses, out[1] the smallest i without a row, out[2] the i whose row is not row i
+__global__ __launch_bounds__(256) void k_ids_lookup(const int *__restrict__ want, int64_t N, int lo, int64_t span, const int *__restrict__ table,
+                                                    int *__restrict__ row_of, unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned s_miss[4], s_moved[4];
+    __shared__ int s_first[4];
+    unsigned miss = 0, moved = 0;
+    int first = 2147483647; // (N < 2^31 - 1: every index is below)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t d = (int64_t)want[i] - lo;
+        const int r = d >= 0 && d < span ? table[d] : -1;
+        row_of[i] = r;
+        if (r < 0) { ++miss; first = min(first, (int)i); }
+        moved += (int64_t)r != i ? 1u : 0u;
+    }
+    for (int o = 32; o > 0; o >>= 1) { miss += __shfl_xor(miss, o); moved += __shfl_xor(moved, o); first = min(first, __shfl_xor(first, o)); }
+    if ((threadIdx.x & 63) == 0) { s_miss[threadIdx.x >> 6] = miss; s_moved[threadIdx.x >> 6] = moved; s_first[threadIdx.x >> 6] = first; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned m = s_miss[0] + s_miss[1] + s_miss[2] + s_miss[3], v = s_moved[0] + s_moved[1] + s_moved[2] + s_moved[3];
+        if (m) {
+            atomicAdd(&out[0], (unsigned long long)m);
+            atomicMin(&out[1], (unsigned long long)min(min(s_first[0], s_first[1]), min(s_first[2], s_first[3])));
+        }
+        if (v) atomicAdd(&out[2], (unsigned long long)v);
+    }
+}
+
 static double box_volume(const DBox &b)
 {
     const double *h = b.h;
@@ -251,6 +313,56 @@ int mdh_permute(const void *in, const int *perm, int64_t N, int elem_bytes, int 
     }
     MDH_HIP(hipGetLastError());
     return sc.finish(space);
+}
+
+int mdh_match_ids(const int *want, const int *have, int64_t N, int *row_of, int64_t *status4, int space, void *stream)
+{
+    if (N < 0 || N >= 2147483647LL || !status4 || (N > 0 && (!want || !have || !row_of))) {
+        set_error("mdh_match_ids: null pointer or invalid N");
+        return MDH_ERR_ARG;
+    }
+    status4[0] = 0; status4[1] = -1; status4[2] = 0; status4[3] = 0;
+    if (N == 0)
+        return MDH_OK;
+    Scope sc(stream);
+    if (sc.failed())
+        return sc.error();
+    hipStream_t st = sc.stream();
+    const int *dwant = sc.stage_in(want, (size_t)N, space), *dhave = sc.stage_in(have, (size_t)N, space);
+    int *drow = sc.stage(row_of, (size_t)N, space, false, true);
+    int *lohi = sc.alloc_n<int>(2);
+    unsigned long long *dout = sc.alloc_n<unsigned long long>(3);
+    if (sc.failed())
+        return sc.error();
+    const int start[2] = {2147483647, -2147483647 - 1};
+    int range[2] = {0, 0};
+    MDH_HIP(hipMemcpyAsync(lohi, start, sizeof(start), hipMemcpyHostToDevice, st));
+    const dim3 grid(grid_for(N, 256)), few(std::min(grid_for(N, 256), IDS_BLOCKS)), block(256);
+    hipLaunchKernelGGL(k_ids_range, few, block, 0, st, dhave, N, lohi);
+    MDH_HIP(hipMemcpyAsync(range, lohi, sizeof(range), hipMemcpyDeviceToHost, st));
+    MDH_HIP(hipStreamSynchronize(st));
+    const int64_t span = (int64_t)range[1] - (int64_t)range[0] + 1;
+    if (span > 4 * N) { // ids too sparse for a table of rows: the caller sorts them
+        status4[3] = 1;
+        return MDH_OK;
+    }
+    int *table = sc.alloc_n<int>((size_t)span);
+    if (sc.failed())
+        return sc.error();
+    const unsigned long long zero[3] = {0ull, ~0ull, 0ull};
+    MDH_HIP(hipMemsetAsync(table, 0xFF, (size_t)span * sizeof(int), st));
+    MDH_HIP(hipMemcpyAsync(dout, zero, sizeof(zero), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ids_fill, grid, block, 0, st, dhave, N, range[0], span, table);
+    hipLaunchKernelGGL(k_ids_lookup, few, block, 0, st, dwant, N, range[0], span, table, drow, dout);
+    MDH_HIP(hipGetLastError());
+    unsigned long long host[3] = {0, 0, 0};
+    MDH_HIP(hipMemcpyAsync(host, dout, sizeof(host), hipMemcpyDeviceToHost, st));
+    MDH_TRY(sc.finish(space));
+    MDH_HIP(hipStreamSynchronize(st));
+    status4[0] = (int64_t)host[0];
+    status4[1] = host[0] ? (int64_t)host[1] : -1;
+    status4[2] = (int64_t)host[2];
+    return MDH_OK;
 }
 
 int mdh_gather_positions(const double *x, const double *y, const double *z, const int *perm, int64_t N, double *xs, double *ys, double *zs,

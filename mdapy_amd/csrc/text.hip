@@ -12,9 +12,13 @@
 // Everything is byte / integer work bound by HBM: a 500 MB dump is read twice and ~0.3 GB of columns written.
 // Fields the device cannot decide (more than 19 significant digits on a rounding boundary, nan/inf, > 8 character
 // strings) are listed in `redo` and re-parsed by the caller with the host's float(): results are what the reference gets.
+// A LAMMPS data file (load_save.py:1036-1323) has sections in any order where a dump has nine header lines: k_scan_sections
+// finds the first line of each section word in one more pass over the resident text (mdh_scan_sections).
 #include "common.hpp"
 #include "grid.hpp"
 #include "text_parse.hpp"
+#include "text_sections.hpp"
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -136,6 +140,7 @@ static int device_pow5(const uint64_t **out)
 // kernels
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int TXT_THREADS = 256, TXT_PER_LANE = 16, TXT_BLOCK_BYTES = TXT_THREADS * TXT_PER_LANE;
+constexpr int SCAN_BLOCKS = 4096; // workgroups of k_scan_sections: 16 on each of the 256 compute units
 
 __device__ __forceinline__ unsigned newline_count16(const char *__restrict__ text, int64_t at, int64_t nbytes)
 {
@@ -250,9 +255,141 @@ __global__ __launch_bounds__(256) void k_parse_rows(const char *__restrict__ tex
         atomicAdd(&status[1], 1ull); // a short row
 }
 
+// A LAMMPS data file (src/mdapy/load_save.py:1064-1092): every line start of the text — byte 0 and one past every '\n' — is
+// tried against the section words (text_sections.hpp); a match lowers that word's slot to the line's offset with a 64-bit
+// atomic minimum, so the slots end as the FIRST line of each word in whatever order the waves ran.  A lane looks at the 16
+// bytes it loads and at the byte before them; only a line start reads further.  The newlines are counted on the way; a workgroup
+// strides over the 4 KB blocks of the text and adds its count once, at the end (one word takes ~90 atomics per microsecond: a
+// workgroup per block of a 500 MB text would queue 133 000 of them, 1.5 ms).
+__global__ __launch_bounds__(TXT_THREADS) void k_scan_sections(const char *__restrict__ text, int64_t nbytes, int64_t nblk,
+                                                               mdtext::SectionWords words, unsigned long long *__restrict__ first,
+                                                               unsigned long long *__restrict__ newlines)
+{
+    __shared__ unsigned part[TXT_THREADS / 64];
+    unsigned c = 0;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) { // (a workgroup-uniform trip count: every lane takes part in the shuffle)
+        const int64_t at = (blk * TXT_THREADS + threadIdx.x) * TXT_PER_LANE;
+        const bool live = at < nbytes;
+        unsigned wds[4] = {0u, 0u, 0u, 0u}; // the lane's 16 bytes, little-endian; bytes past the end of the text stay 0
+        if (live) {
+            if (at + TXT_PER_LANE <= nbytes && ((reinterpret_cast<uintptr_t>(text + at) & 15) == 0)) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(text + at);
+                wds[0] = v.x; wds[1] = v.y; wds[2] = v.z; wds[3] = v.w;
+            } else {
+                for (int k = 0; k < TXT_PER_LANE; ++k)
+                    if (at + k < nbytes) wds[k >> 2] |= (unsigned)(unsigned char)text[at + k] << (8 * (k & 3));
+            }
+        }
+        // the byte before the lane's 16: the last one of the lane below; the first lane of a wave reads it (byte 0 starts a line)
+        unsigned prev = __shfl_up(wds[3] >> 24, 1);
+        if ((threadIdx.x & 63) == 0) prev = live && at > 0 ? (unsigned)(unsigned char)text[at - 1] : (unsigned)'\n';
+        if (live) {
+            unsigned nl = 0; // bit k: byte k is a line feed
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned x = wds[q] ^ 0x0A0A0A0Au; // a zero byte where the line feeds were
+                const unsigned z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu); // 0x80 in exactly those bytes
+                nl |= ((((z >> 7) * 0x00204081u) >> 21) & 0xFu) << (4 * q); // bits 0, 8, 16, 24 gathered into four
+            }
+            c += (unsigned)__popc(nl);
+            const int64_t left = nbytes - at; // bytes of the text in this lane's 16
+            unsigned starts = ((nl << 1) | (prev == '\n' ? 1u : 0u)) & (left >= TXT_PER_LANE ? 0xFFFFu : ((1u << left) - 1u));
+            while (starts) { // (most lanes: no line starts here, or one)
+                const int k = __ffs((int)starts) - 1;
+                starts &= starts - 1;
+                const unsigned word = k < 8 ? (k < 4 ? wds[0] : wds[1]) : (k < 12 ? wds[2] : wds[3]);
+                const unsigned b = (word >> (8 * (k & 3))) & 0xFFu; // the line's first byte: a digit, a sign, '#', '\n' end it here
+                if ((b >= words.lo && b <= words.hi) || mdtext::sec_blank((char)b)) {
+                    const int w = mdtext::match_section(text, at + k, nbytes, words);
+                    if (w >= 0) atomicMin(&first[w], (unsigned long long)(at + k));
+                }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned total = part[0] + part[1] + part[2] + part[3];
+        if (total) atomicAdd(newlines, (unsigned long long)total);
+    }
+}
+
 } // namespace mdh
 
 using namespace mdh;
+
+static int scan_arguments(const char *what, const char *text, int64_t nbytes, const char *const *words, int nwords, const int64_t *first_offset,
+                          const int64_t *line_count, mdtext::SectionWords &table)
+{
+    if (nbytes < 0 || (nbytes > 0 && !text) || !first_offset || !line_count) {
+        set_error(std::string(what) + ": null pointer or negative size");
+        return MDH_ERR_ARG;
+    }
+    if (!mdtext::section_words_init(table, words, nwords)) {
+        set_error(std::string(what) + ": 1..32 words of 1..15 bytes without blanks");
+        return MDH_ERR_ARG;
+    }
+    if (nbytes > 2147483647LL * mdh::TXT_BLOCK_BYTES / 2) {
+        set_error(std::string(what) + ": text too large for one call");
+        return MDH_ERR_ARG;
+    }
+    return MDH_OK;
+}
+
+extern "C" int mdh_scan_sections(const char *text, int64_t nbytes, int text_space, const char *const *words, int nwords, int64_t *first_offset,
+                                 int64_t *line_count, void *stream)
+{
+    mdtext::SectionWords table;
+    MDH_TRY(scan_arguments("mdh_scan_sections", text, nbytes, words, nwords, first_offset, line_count, table));
+    for (int k = 0; k < nwords; ++k) first_offset[k] = -1;
+    *line_count = 0;
+    if (nbytes == 0)
+        return MDH_OK;
+    Scope sc(stream);
+    if (sc.failed())
+        return sc.error();
+    hipStream_t st = sc.stream();
+    const char *dtext = sc.stage_in(text, (size_t)nbytes, text_space);
+    unsigned long long *dout = sc.alloc_n<unsigned long long>(mdtext::SEC_MAX_WORDS + 1); // the words' slots, then the newline count
+    if (sc.failed())
+        return sc.error();
+    MDH_HIP(hipMemsetAsync(dout, 0xFF, mdtext::SEC_MAX_WORDS * sizeof(unsigned long long), st));
+    MDH_HIP(hipMemsetAsync(dout + mdtext::SEC_MAX_WORDS, 0, sizeof(unsigned long long), st));
+    const int64_t nblk = (nbytes + TXT_BLOCK_BYTES - 1) / TXT_BLOCK_BYTES;
+    {
+        ProfRange pr("k_scan_sections", st);
+        hipLaunchKernelGGL(k_scan_sections, dim3((unsigned)std::min<int64_t>(nblk, SCAN_BLOCKS)), dim3(TXT_THREADS), 0, st, dtext, nbytes, nblk, table, dout,
+                           dout + mdtext::SEC_MAX_WORDS);
+    }
+    MDH_HIP(hipGetLastError());
+    unsigned long long host[mdtext::SEC_MAX_WORDS + 1];
+    char last = 0;
+    MDH_HIP(hipMemcpyAsync(host, dout, sizeof(host), hipMemcpyDeviceToHost, st));
+    MDH_HIP(hipMemcpyAsync(&last, dtext + nbytes - 1, 1, hipMemcpyDeviceToHost, st));
+    MDH_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < nwords; ++k) first_offset[k] = (int64_t)host[k]; // (an untouched slot is all ones: -1)
+    *line_count = (int64_t)host[mdtext::SEC_MAX_WORDS] + (last == '\n' ? 0 : 1);
+    return MDH_OK;
+}
+
+// host twin of the scan (tests pin the matcher against a plain line loop without a GPU)
+extern "C" int mdh_debug_scan_sections(const char *text, int64_t nbytes, const char *const *words, int nwords, int64_t *first_offset, int64_t *line_count)
+{
+    mdtext::SectionWords table;
+    MDH_TRY(scan_arguments("mdh_debug_scan_sections", text, nbytes, words, nwords, first_offset, line_count, table));
+    for (int k = 0; k < nwords; ++k) first_offset[k] = -1;
+    int64_t newlines = 0;
+    for (int64_t at = 0; at < nbytes; ++at) {
+        if (at == 0 || text[at - 1] == '\n') {
+            const int w = mdtext::match_section(text, at, nbytes, table);
+            if (w >= 0 && first_offset[w] < 0) first_offset[w] = at;
+        }
+        newlines += text[at] == '\n' ? 1 : 0;
+    }
+    *line_count = nbytes == 0 ? 0 : newlines + (text[nbytes - 1] == '\n' ? 0 : 1);
+    return MDH_OK;
+}
 
 extern "C" int mdh_debug_text_pow5(int q, uint64_t *out2)
 {
