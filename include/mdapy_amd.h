@@ -750,6 +750,32 @@ int mdh_lindemann_global(const double *pos, int64_t F, int64_t N, double *pair_s
 int mdh_lindemann_all(const double *pos, int64_t F, int64_t N, double *pair_mean, double *pair_var, double *lindemann_frame,
                       double *lindemann_atom, int segments, int space, void *stream);
 
+/* ---- _sample (potential_tool.fps_sample, potential_tool.PCA) ---------- */
+/* Farthest-point sampling of the rows of x (N, D) f64, C-contiguous             src/mdapy/potential_tool.py:404-445
+ * picks_host (n_sample i32, HOST memory): [0] = start; [s + 1] = the row whose minimum squared distance to rows [0 .. s] is
+ * largest, the lowest such row on equal values.  Nothing is excluded: a row already picked has minimum 0.  The squared distance
+ * of row a to row b is acc = 0; acc = acc + (a_k - b_k) * (a_k - b_k) for k = 0 .. D-1 — one accumulator, ascending k, IEEE
+ * binary64, no contraction — on every path and for every launch shape.  The reference compares the roots of these sums.
+ * min_d2 (N f64, may be NULL: not wanted) = every row's minimum after the n_sample - 1 passes, i.e. over picks [0 .. n_sample-2];
+ * +inf everywhere when n_sample is 1.
+ * path: 0 the library chooses, 1 grid (one launch per pick; the workgroup that draws the last ticket of a pass reduces the
+ * workgroups' candidates, nothing waits on another workgroup), 2 one workgroup looping over the picks (at most 512 columns and
+ * 1 048 576 entries, MDH_ERR_ARG beyond).  Both give the same bits.  *path_host (may be NULL) = the path taken, 1 or 2.
+ * N outside 1 .. 2^31 - 1025, D outside 1 .. 1024, n_sample outside 1 .. N, start outside [0, N) return MDH_ERR_ARG before any
+ * device work; so does, after the run, a table in which the first pass met a value that is not finite (no pass, no check, when
+ * n_sample is 1).  Scratch: N f64 (without min_d2), n_sample i32, 2 048 candidates.  Synchronises the stream. */
+int mdh_fps_sample(const double *x, int64_t N, int64_t D, int64_t n_sample, int64_t start, int path, int *picks_host,
+                   double *min_d2, int *path_host, int space, void *stream);
+/* The device halves of a principal component analysis                          src/mdapy/potential_tool.py:381-401
+ * moments: mean (D) f64 = the column sums / N; cov (D, D) f64 = the sum over the rows of (x[a] - mean[a]) * (x[b] - mean[b])
+ * / (N - 1), symmetric to the bit.  Every sum is taken over the rows of a workgroup in index order, then over the workgroups in
+ * index order (no floating-point atomics): the same input gives the same bits on every run.  N >= 2, 1 <= D <= 128. */
+int mdh_pca_moments(const double *x, int64_t N, int64_t D, double *mean, double *cov, int space, void *stream);
+/* project: out (N, C) f64, [i, c] = the sum over k = 0 .. D-1, in that order, of (x[i, k] - mean[k]) * components[k, c];
+ * components (D, C) f64, 1 <= C <= D <= 128, N >= 1. */
+int mdh_pca_project(const double *x, int64_t N, int64_t D, const double *mean, const double *components, int64_t C, double *out,
+                    int space, void *stream);
+
 /* ---- _sqs -------------------------------------------------------------- */
 /* Special quasirandom structures: cluster correlations of a lattice alloy, and a Monte-Carlo search over R independent chains
  * (replaces _sqs.SQSEngine's correlations / per_channel_delta / objective / run_mc, src/sqs.cpp:246-509).  The header comment of

@@ -134,6 +134,9 @@ _SIGNATURES = {
     "mdh_ws_occupancy": [vp, i64, i64, vp, vp, vp, vp, vp, cint, vp],
     "mdh_lindemann_global": [vp, i64, i64, vp, vp, vp, cint, vp],
     "mdh_lindemann_all": [vp, i64, i64, vp, vp, vp, vp, cint, cint, vp],
+    "mdh_fps_sample": [vp, i64, i64, i64, i64, cint, vp, vp, vp, cint, vp],
+    "mdh_pca_moments": [vp, i64, i64, vp, vp, cint, vp],
+    "mdh_pca_project": [vp, i64, i64, vp, vp, i64, vp, cint, vp],
     "mdh_sqs_count": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, cint, vp],
     "mdh_sqs_run": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, dbl, i64, C.c_uint64, i64, vp, vp, vp, vp, vp, cint, vp],
     "mdh_msd_window": [vp, i64, i64, i64, vp, vp, cint, vp],

@@ -400,6 +400,7 @@ void warm_wcp(hipStream_t st);
 void warm_knn(hipStream_t st);
 void warm_wigner_seitz(hipStream_t st);
 void warm_lindemann(hipStream_t st);
+void warm_sample(hipStream_t st);
 void warm_sqs(hipStream_t st);
 void warm_msd(hipStream_t st);
 void warm_unwrap(hipStream_t st);
@@ -533,6 +534,7 @@ int mdh_warm(void)
     mdh::warm_knn(nullptr);
     mdh::warm_wigner_seitz(nullptr);
     mdh::warm_lindemann(nullptr);
+    mdh::warm_sample(nullptr);
     mdh::warm_sqs(nullptr);
     mdh::warm_msd(nullptr);
     mdh::warm_unwrap(nullptr);

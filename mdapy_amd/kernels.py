@@ -37,6 +37,9 @@ from . import _polycrystal as polycrystal
 from . import _ptm as ptm
 from . import _rdf as rdf
 from . import _repeat_cell as repeat_cell
+# (not in NAMES either: the reference's farthest-point sampling and PCA are numpy, the oracle has neither; their tests install a
+# restatement as kernels.sample)
+from . import _sample as sample
 from . import _sbo as sbo
 from . import _sfc as sfc
 # (not in NAMES either: the oracle has no SQS engine; its tests install a restatement as kernels.sqs)
