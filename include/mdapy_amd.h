@@ -613,6 +613,34 @@ int mdh_nep(const double *x, const double *y, const double *z, const int *type, 
             const double *model, const int *head12_host, const double *zbl3_host, int64_t n_real, double *energy, double *force, double *virial,
             double *virial_sum9, double *descriptor, double *latent, int space, void *stream);
 
+/* replaces _nepcal.NEPCalculator.calculate for charge models (qNEP)       src/neppy.cpp, extern/NEPCPU/nep.cpp:2434-2602
+ * mdh_nep for the charge-aware models nep4_charge1 / 2 / 3: the network's second output is the atom's charge, the mean charge of the
+ * first n_real atoms is removed, and the energies, forces and virials gain the electrostatic part of the charges — mode 1 the Ewald
+ * sum (k-space and real space), mode 2 its k-space part alone, mode 3 a real-space sum shifted to vanish with its slope at the
+ * cutoff — with alpha = pi / rc_coulomb and K = 14.399645 eV A.  Every argument of mdh_nep means what it means there; further:
+ * head12_host[11] is the charge mode 1..3; the block holds per type w0, b0, w1 (energy, neurons), w1 (charge, neurons) and the
+ * type's bias, and sqrt(epsilon_inf) stands before the common bias.
+ * kcell9_host (host f64, rows the cell vectors): the cell whose reciprocal vectors b_i the k-space sum runs over, k = n1 b1 + n2 b2 +
+ * n3 b3 with 0 < k^2 < (2 pi alpha)^2, |n_i| <= alpha |a_i|, in the half space n1 > 0, or n1 = 0 and n2 > 0, or n1 = n2 = 0 and
+ * n3 > 0.  The structure factor sums the first n_real atoms; every other pass runs for all N rows (a replica's copies get the charge
+ * and the potential the passes give them).  max_kpoints: the k-points the call may hold in scratch (48 B each).
+ * rc_coulomb: the model's largest radial cutoff; real-space sums take the list's entries with dist < rc_coulomb.
+ * charge (N) f64: the charges, mean removed.  bec (N x 9, row-major) f64: sqrt(epsilon_inf) (q_i 1 + 1/2 sum_j r_ij (x) (g_ij + g_ji)),
+ * g_ij = dq_i / dr_ij from the pair pass with the charge's derivatives, g_ji looked up where row j names i.  Both may be NULL.
+ * All f64, product then add, no atomics; every sum runs in an order that depends on the list, N, n_real and the k-points alone: the
+ * same bits on every run.  The k-space part costs one term per (atom, k-point) and the number of k-points grows with the volume:
+ * O(N^2).  e^{ik.r} is made from per-axis phase factors e^{i n b_d.r}: the structure factor keeps their tables (one entry per n_d in
+ * range, 16 B) for a few atoms at a time in 48 KB of LDS.  The k-points are made on the host and uploaded on every call; the call
+ * waits for that upload.
+ * MDH_ERR_ARG before any launch: what mdh_nep names, a charge mode outside 1..3, a block whose length does not follow from the
+ * header (with the charge's weights), rc_coulomb not positive, a k-space cell without volume, more k-points than max_kpoints, a
+ * cell so long that one atom's phase tables exceed 48 KB (the three ranges of n_d together above 3072 entries). */
+int mdh_nep_charge(const double *x, const double *y, const double *z, const int *type, int64_t N, const int *type_map_host, int nfile,
+                   const double *box9, const double *origin3, const int *boundary3, const int *verlet, const double *dist, const int *nn,
+                   int64_t M, const double *model, const int *head12_host, const double *zbl3_host, const double *kcell9_host,
+                   double rc_coulomb, int64_t max_kpoints, int64_t n_real, double *energy, double *force, double *virial, double *virial_sum9,
+                   double *charge, double *bec, double *descriptor, double *latent, int space, void *stream);
+
 /* ---- _fire ------------------------------------------------------------ */
 /* The arithmetic of the FIRE minimizer (src/mdapy/minimizer.py:270-375 does it in numpy) on (n, 3) row-major f64 arrays; no
  * reference counterpart in C++.  f64, no contraction.  The scalars the steps hand to one another live in a RECORD of

@@ -18,7 +18,7 @@ from .warren_cowley_parameter import WarrenCowleyParameter
 from .atomic_strain import AtomicStrain
 from .calculator import CalculatorMP
 from .eam import EAM
-from .nep import NEP
+from .nep import NEP, QNEP
 from . import minimizer
 from .minimizer import FIRE
 from .chill_plus import ChillPlus
@@ -37,7 +37,7 @@ from .parallel import get_num_threads
 __all__ = [
     "Box", "Frame", "System", "Neighbor", "NearestNeighbor", "CommonNeighborAnalysis", "CentroSymmetryParameter",
     "IdentifyDiamondStructure", "SteinhardtBondOrientation", "PolyhedralTemplateMatching", "RadialDistributionFunction", "WarrenCowleyParameter",
-    "AtomicStrain", "CalculatorMP", "EAM", "NEP", "FIRE", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
+    "AtomicStrain", "CalculatorMP", "EAM", "NEP", "QNEP", "FIRE", "ChillPlus", "WignerSeitzAnalysis", "LindemannParameter", "MeanSquaredDisplacement", "VoidAnalysis",
     "Trajectory", "unwrap_trajectory", "VDW_RADII", "vdw_radius",
     "build_crystal", "build_hea", "build_hea_fromsystem", "SQS", "CreatePolycrystal", "get_num_threads",
 ]

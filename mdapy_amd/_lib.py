@@ -114,6 +114,8 @@ _SIGNATURES = {
     "mdh_eam": [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, cint, cint, dbl, cint, dbl, dbl, cint, vp, vp, vp, i64, vp,
                 cint, vp],
     "mdh_nep": [vp, vp, vp, vp, i64, vp, cint, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, cint, vp],
+    "mdh_nep_charge": [vp, vp, vp, vp, i64, vp, cint, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, dbl, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                       cint, vp],
     "mdh_fire_dots": [vp, vp, i64, vp, cint, vp],
     "mdh_fire_kick": [vp, vp, i64, dbl, cint, vp, cint, vp],
     "mdh_fire_mix": [vp, vp, i64, dbl, dbl, cint, dbl, vp, cint, vp],

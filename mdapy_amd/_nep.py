@@ -57,3 +57,35 @@ def calculate(x, y, z, types, type_map, box, origin, boundary, rows, dist, count
                              model.head.ctypes.data, model.zbl.ctypes.data, N if n_real is None else int(n_real), out(energy), out(force),
                              out(virial), out(virial_sum), out(descriptor), out(latent), c.space, c.stream)
     c.done(rc_)
+
+
+def calculate_charge(x, y, z, types, type_map, box, origin, boundary, rows, dist, counts, model, kcell, rc_coulomb, energy=None, force=None,
+                     virial=None, virial_sum=None, charge=None, bec=None, descriptor=None, latent=None, n_real=None, max_kpoints=1 << 24):
+    """``calculate`` for a charge model (``mdh_nep_charge``): ``model`` holds the block of ``QNEP._model_arrays`` (the last header word
+    the charge mode), ``kcell`` (3, 3, host) is the cell whose reciprocal vectors the k-space sum runs over — the real cell, where the
+    list is a replica's —, ``rc_coulomb`` the model's largest radial cutoff (alpha = pi / rc_coulomb); ``charge`` (N,) and ``bec``
+    (N, 9) are further outputs.  The call may hold up to ``max_kpoints`` k-points (48 B each)."""
+    N, M = int(rows.shape[0]), int(rows.shape[1])
+    _lib.same_rows("NEP.calculate_charge", N, x=x, y=y, z=z, types=types, dist=dist, counts=counts, energy=energy, force=force, virial=virial,
+                   charge=charge, bec=bec, descriptor=descriptor, latent=latent)
+    for name, a, shape in (("dist", dist, (N, M)), ("force", force, (N, 3)), ("virial", virial, (N, 9)), ("virial_sum", virial_sum, (9,)),
+                           ("charge", charge, (N,)), ("bec", bec, (N, 9)), ("descriptor", descriptor, (N, model.dim)),
+                           ("latent", latent, (N, model.neurons))):
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError(f"NEP.calculate_charge: {name} of shape {tuple(a.shape)} where {shape} is required")
+    if virial_sum is not None and virial is None:
+        raise ValueError("NEP.calculate_charge: virial_sum needs virial")
+    type_map = np.ascontiguousarray(type_map, dtype=i32)
+    kcell = np.ascontiguousarray(kcell, dtype=f64)
+    if kcell.shape != (3, 3):
+        raise ValueError("NEP.calculate_charge: kcell of shape (3, 3) is required")
+    keep, (pb, po, pp) = _lib.host_box(box, origin, boundary)
+    c = Call(x, y, z, types, rows, dist, counts, energy, force, virial, virial_sum, charge, bec, descriptor, latent)
+    block = model._block(c.space == _lib.DEVICE)
+    out = lambda a: None if a is None else c.out(a, f64, upload=False)
+    rc_ = _lib.lib().mdh_nep_charge(c.inp(x, f64), c.inp(y, f64), c.inp(z, f64), c.inp(types, i32), N, type_map.ctypes.data, len(type_map),
+                                    pb, po, pp, c.inp(rows, i32), c.inp(dist, f64), c.inp(counts, i32), M, c.inp(block, f64),
+                                    model.head.ctypes.data, model.zbl.ctypes.data, kcell.ctypes.data, float(rc_coulomb), int(max_kpoints),
+                                    N if n_real is None else int(n_real), out(energy), out(force), out(virial), out(virial_sum), out(charge),
+                                    out(bec), out(descriptor), out(latent), c.space, c.stream)
+    c.done(rc_)

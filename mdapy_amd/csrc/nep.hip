@@ -27,14 +27,10 @@
 //                        replica's copies by their own index, so the entry is unique), reads f_ji there, and the lanes' partial
 //                        force and virial are added as a butterfly
 // All arithmetic is f64, product then add (-ffp-contract=off).
-#include "common.hpp"
-#include <algorithm>
-#include <vector>
+#include "nep_core.hpp"
 
 namespace mdh {
 
-constexpr int NEP_MAX_N = 16, NEP_MAX_K = 17, NEP_MAX_NEURON = 128, NEP_MAX_DIM = NEP_MAX_N + 6 * NEP_MAX_N, NEP_MAX_FILE_TYPES = 96;
-constexpr double NEP_PI = 3.14159265358979323846;
 // W_lm = (2l+1)/(4 pi) (2 - delta_m0) (l-m)!/(l+m)! / a_lm^2, p_lm = a_lm d^m P_l / dz^m (addition theorem of the Legendre
 // polynomials); the rational factor per (l, m):
 //   l = 1: 1, 1 | l = 2: 1/4, 3, 3/4 | l = 3: 1/4, 3/8, 15/4, 5/8 | l = 4: 1/64, 5/8, 5/16, 35/8, 35/64
@@ -53,30 +49,7 @@ __device__ constexpr double NEP_C4[5] = {-0.007499480826664, -0.134990654879954,
 __device__ constexpr double NEP_C5[3] = {0.026596810706114, 0.053193621412227, 0.026596810706114};
 // the universal ZBL screening function (Ziegler, Biersack, Littmark), 1 / 0.46850 A, e^2 / (4 pi eps0) in eV A
 __device__ constexpr double ZBL_A[4] = {0.18175, 0.50986, 0.28022, 0.02817}, ZBL_B[4] = {3.1998, 0.94229, 0.4029, 0.20162};
-constexpr double ZBL_LENGTH_INV = 2.134563, NEP_COULOMB = 14.399645;
-
-struct NepModel {
-    int T, NR, KR, NA, KA, L3, L4, L5, H, dim, mode, nfile;
-    int o_rc_r, o_rc_a, o_z, o_rcov, o_scaler, o_cr, o_ca, o_net, net_stride, o_b1;
-    double zbl_inner, zbl_outer, zbl_factor;
-    const double *p;
-};
-// a type of the FILE -> the model's own type, -1: none; by value, in the kernel's arguments
-struct NepTypeMap { signed char local[NEP_MAX_FILE_TYPES]; };
-
-// the minimum image of a difference.  Orthogonal boxes take d - L floor(d / L + 0.5) with the quotient as a product: the twelve
-// thresholds of common.hpp's bit-exact form would sit in scalar registers beside the model's words, which are short here
-template <bool TRI>
-__device__ __forceinline__ void nep_image(const DBox &b, double &dx, double &dy, double &dz)
-{
-    if (TRI) {
-        pbc<true>(b, dx, dy, dz);
-    } else {
-        if (b.pbc[0]) dx -= b.h[0] * floor(dx * b.hi[0] + 0.5);
-        if (b.pbc[1]) dy -= b.h[4] * floor(dy * b.hi[4] + 0.5);
-        if (b.pbc[2]) dz -= b.h[8] * floor(dz * b.hi[8] + 0.5);
-    }
-}
+constexpr double ZBL_LENGTH_INV = 2.134563;
 
 // g = sum_k c[k] f_k(d) and its derivative, d < rc
 __device__ __forceinline__ void radial_function(double d, double rc, const double *__restrict__ c, int K, double &g, double &dg)
@@ -175,15 +148,6 @@ __device__ __forceinline__ bool zbl_pair(const NepModel &m, int ti, int tj, doub
     return true;
 }
 
-// the sum of v over the W lanes of a group, the same bits in every lane: a butterfly, so the order depends on W alone
-template <int W>
-__device__ __forceinline__ double group_sum(double v)
-{
-#pragma unroll
-    for (int step = 1; step < W; step <<= 1) v += __shfl_xor(v, step, 64);
-    return v;
-}
-
 // positions and the model's own type of every atom as one 32-byte record (w = the type, -1: none)
 __global__ __launch_bounds__(256) void k_nep_pack(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                   const int *__restrict__ type, NepTypeMap map, int nfile, int T, int64_t N,
@@ -199,16 +163,57 @@ __global__ __launch_bounds__(256) void k_nep_pack(const double *__restrict__ x, 
     out[i] = Pos4{x[i], y[i], z[i], (double)local};
 }
 
-template <int W, bool TRI>
+// A_nk = dU / ds_nk of one lane's n from the group's Fp row (in LDS) and the lane's sums s; 24 numbers to out
+__device__ __forceinline__ void nep_write_A(const double (&s)[24], const double *__restrict__ fp_row, const NepModel &m, int lane, bool mine,
+                                            double *__restrict__ out)
+{
+    double A[24];
+    int first = 0;
+#pragma unroll
+    for (int k = 0; k < 24; ++k) A[k] = 0.0;
+    for (int l = 1; l <= m.L3; ++l) {
+        const double fp = 2.0 * fp_row[m.NR + (l - 1) * m.NA + lane];
+#pragma unroll
+        for (int k = 0; k < 24; ++k)
+            if (k >= first && k < first + 2 * l + 1) A[k] = fp * (NEP_W[k] * s[k]);
+        first += 2 * l + 1;
+    }
+    int order = m.L3;
+    if (m.L4 == 2) {
+        const double F = fp_row[m.NR + order * m.NA + lane];
+        A[3] += F * (3.0 * NEP_C4[0] * s[3] * s[3] + NEP_C4[1] * (s[4] * s[4] + s[5] * s[5]) + NEP_C4[2] * (s[6] * s[6] + s[7] * s[7]));
+        A[4] += F * (2.0 * NEP_C4[1] * s[3] * s[4] - 2.0 * NEP_C4[3] * s[6] * s[4] + NEP_C4[4] * s[5] * s[7]);
+        A[5] += F * (2.0 * NEP_C4[1] * s[3] * s[5] + 2.0 * NEP_C4[3] * s[6] * s[5] + NEP_C4[4] * s[4] * s[7]);
+        A[6] += F * (2.0 * NEP_C4[2] * s[3] * s[6] + NEP_C4[3] * (s[5] * s[5] - s[4] * s[4]));
+        A[7] += F * (2.0 * NEP_C4[2] * s[3] * s[7] + NEP_C4[4] * s[4] * s[5]);
+        ++order;
+    }
+    if (m.L5 == 1) {
+        const double F = fp_row[m.NR + order * m.NA + lane];
+        const double pp = s[1] * s[1] + s[2] * s[2], s0 = s[0] * s[0];
+        A[0] += F * (4.0 * NEP_C5[0] * s0 * s[0] + 2.0 * NEP_C5[1] * s[0] * pp);
+        A[1] += F * (2.0 * NEP_C5[1] * s0 * s[1] + 4.0 * NEP_C5[2] * pp * s[1]);
+        A[2] += F * (2.0 * NEP_C5[1] * s0 * s[2] + 4.0 * NEP_C5[2] * pp * s[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < 24; ++k) out[k] = mine ? A[k] : 0.0;
+}
+
+// Q: a charge model — the network's second output (charge, before the frame's mean is removed) and its derivatives FpRq, Aq, the
+// twins of FpR and Aout.  A is linear in Fp, so the two sets are written one after the other from the same 24 sums.
+template <int W, bool TRI, bool Q>
 __global__ __launch_bounds__(64) void k_nep_descriptor(const int *__restrict__ verlet, const double *__restrict__ dist, const int *__restrict__ nn,
                                                        int64_t N, int64_t M, DBox b, const Pos4 *__restrict__ rec, NepModel m,
                                                        double *__restrict__ energy, double *__restrict__ FpR, double *__restrict__ Aout,
-                                                       double *__restrict__ descriptor, double *__restrict__ latent)
+                                                       double *__restrict__ descriptor, double *__restrict__ latent,
+                                                       double *__restrict__ charge, double *__restrict__ FpRq, double *__restrict__ Aq)
 {
     constexpr int G = 64 / W;
     __shared__ double sq[G][NEP_MAX_DIM];
     __shared__ double lat[G][NEP_MAX_NEURON];
     __shared__ double slope[G][NEP_MAX_NEURON];
+    __shared__ double hidden[Q ? G : 1][Q ? NEP_MAX_NEURON : 1];  // tanh(..): the charge's output and slope follow from it
+    double(*sqq)[NEP_MAX_NEURON] = lat;  // Fp_q takes the latent space's place once that is written out (dim <= 112 < 128)
     const int lane = threadIdx.x % W, grp = threadIdx.x / W;
     const int64_t i = (int64_t)blockIdx.x * G + grp;
     const bool on = i < N;
@@ -289,13 +294,15 @@ __global__ __launch_bounds__(64) void k_nep_descriptor(const int *__restrict__ v
         for (int d = lane; d < m.dim; d += W) descriptor[i * m.dim + d] = mine ? sq[grp][d] : 0.0;
     // the network of the atom's type: the neurons dealt over the lanes
     const double *net = m.p + m.o_net + (int64_t)(mine ? ti : 0) * m.net_stride;
-    const double *w0 = net, *b0 = net + (int64_t)m.H * m.dim, *w1 = b0 + m.H;
+    const double *w0 = net, *b0 = net + (int64_t)m.H * m.dim, *w1 = b0 + m.H, *w1q = w1 + m.H, *bias = w1 + (Q ? 2 : 1) * m.H;
     for (int h = lane; h < m.H; h += W) {
         double dot = 0.0;
         for (int d = 0; d < m.dim; ++d) dot += w0[h * m.dim + d] * sq[grp][d];
         const double x = tanh(dot - b0[h]);
         lat[grp][h] = w1[h] * x;
         slope[grp][h] = w1[h] * (1.0 - x * x);
+        if (Q)
+            hidden[grp][h] = x;
     }
     __syncthreads();
     if (latent && on)
@@ -303,58 +310,48 @@ __global__ __launch_bounds__(64) void k_nep_descriptor(const int *__restrict__ v
     if (energy && on && lane == 0) {
         double e = 0.0;
         for (int h = 0; h < m.H; ++h) e += lat[grp][h];
-        energy[i] = mine ? ((e - m.p[m.o_b1]) - w1[m.H]) + ez : 0.0;
+        energy[i] = mine ? ((e - m.p[m.o_b1]) - bias[0]) + ez : 0.0;
     }
+    if (Q && charge && on && lane == 0) {
+        double q = 0.0;
+        for (int h = 0; h < m.H; ++h) q += w1q[h] * hidden[grp][h];
+        charge[i] = mine ? q : 0.0;
+    }
+    if (Q)
+        __syncthreads();
     // Fp_d = dU / dq_d * scaler_d, the inputs dealt over the lanes; they take the descriptor's place in LDS
     for (int d = lane; d < m.dim; d += W) {
         double fp = 0.0;
         for (int h = 0; h < m.H; ++h) fp += slope[grp][h] * w0[h * m.dim + d];
         sq[grp][d] = fp * scaler[d];
+        if (Q) {
+            double fq = 0.0;
+            for (int h = 0; h < m.H; ++h) fq += (w1q[h] * (1.0 - hidden[grp][h] * hidden[grp][h])) * w0[h * m.dim + d];
+            sqq[grp][d] = fq * scaler[d];
+        }
     }
     __syncthreads();
     if (!on || !Aout)
         return;
-    if (radial)
+    if (radial) {
         FpR[i * m.NR + lane] = mine ? sq[grp][lane] : 0.0;
+        if (Q)
+            FpRq[i * m.NR + lane] = mine ? sqq[grp][lane] : 0.0;
+    }
     if (angular) {
-        double A[24];
-        int first = 0;
-#pragma unroll
-        for (int k = 0; k < 24; ++k) A[k] = 0.0;
-        for (int l = 1; l <= m.L3; ++l) {
-            const double fp = 2.0 * sq[grp][m.NR + (l - 1) * m.NA + lane];
-#pragma unroll
-            for (int k = 0; k < 24; ++k)
-                if (k >= first && k < first + 2 * l + 1) A[k] = fp * (NEP_W[k] * s[k]);
-            first += 2 * l + 1;
-        }
-        int order = m.L3;
-        if (m.L4 == 2) {
-            const double F = sq[grp][m.NR + order * m.NA + lane];
-            A[3] += F * (3.0 * NEP_C4[0] * s[3] * s[3] + NEP_C4[1] * (s[4] * s[4] + s[5] * s[5]) + NEP_C4[2] * (s[6] * s[6] + s[7] * s[7]));
-            A[4] += F * (2.0 * NEP_C4[1] * s[3] * s[4] - 2.0 * NEP_C4[3] * s[6] * s[4] + NEP_C4[4] * s[5] * s[7]);
-            A[5] += F * (2.0 * NEP_C4[1] * s[3] * s[5] + 2.0 * NEP_C4[3] * s[6] * s[5] + NEP_C4[4] * s[4] * s[7]);
-            A[6] += F * (2.0 * NEP_C4[2] * s[3] * s[6] + NEP_C4[3] * (s[5] * s[5] - s[4] * s[4]));
-            A[7] += F * (2.0 * NEP_C4[2] * s[3] * s[7] + NEP_C4[4] * s[4] * s[5]);
-            ++order;
-        }
-        if (m.L5 == 1) {
-            const double F = sq[grp][m.NR + order * m.NA + lane];
-            const double pp = s[1] * s[1] + s[2] * s[2], s0 = s[0] * s[0];
-            A[0] += F * (4.0 * NEP_C5[0] * s0 * s[0] + 2.0 * NEP_C5[1] * s[0] * pp);
-            A[1] += F * (2.0 * NEP_C5[1] * s0 * s[1] + 4.0 * NEP_C5[2] * pp * s[1]);
-            A[2] += F * (2.0 * NEP_C5[1] * s0 * s[2] + 4.0 * NEP_C5[2] * pp * s[2]);
-        }
-        double *out = Aout + (i * m.NA + lane) * 24;
-#pragma unroll
-        for (int k = 0; k < 24; ++k) out[k] = mine ? A[k] : 0.0;
+        nep_write_A(s, sq[grp], m, lane, mine, Aout + (i * m.NA + lane) * 24);
+        if (Q)
+            nep_write_A(s, sqq[grp], m, lane, mine, Aq + (i * m.NA + lane) * 24);
     }
 }
 
-template <int W, bool TRI>
+// Q: a charge model's forces — Fp_E + D_i Fp_q and A_E + D_i A_q take the place of Fp and A (D_i: the derivative of the
+// electrostatic energy with respect to the charge of atom i)
+template <int W, bool TRI, bool Q>
 __global__ __launch_bounds__(64) void k_nep_pair(const int *__restrict__ verlet, const double *__restrict__ dist, const int *__restrict__ nn,
                                                  int64_t N, int64_t M, DBox b, const Pos4 *__restrict__ rec, NepModel m,
-                                                 const double *__restrict__ FpR, const double *__restrict__ Ain, double *__restrict__ table)
+                                                 const double *__restrict__ FpR, const double *__restrict__ Ain, double *__restrict__ table,
+                                                 const double *__restrict__ FpRq, const double *__restrict__ Aq, const double *__restrict__ D)
 {
     constexpr int G = 64 / W;
     const int lane = threadIdx.x % W, grp = threadIdx.x / W;
@@ -364,10 +361,19 @@ __global__ __launch_bounds__(64) void k_nep_pair(const int *__restrict__ verlet,
     const int ti = on ? (int)ri.w : -1;
     const int n = on ? min(max(nn[i], 0), (int)M) : 0;
     const bool radial = lane < m.NR, angular = lane < m.NA;
-    const double fpr = (on && radial) ? FpR[i * m.NR + lane] : 0.0;
+    double fpr = (on && radial) ? FpR[i * m.NR + lane] : 0.0;
     double A[24];
 #pragma unroll
     for (int k = 0; k < 24; ++k) A[k] = (on && angular) ? Ain[(i * m.NA + lane) * 24 + k] : 0.0;
+    if (Q) {
+        const double Di = on ? D[i] : 0.0;
+        if (on && radial)
+            fpr += Di * FpRq[i * m.NR + lane];
+        if (on && angular) {
+#pragma unroll
+            for (int k = 0; k < 24; ++k) A[k] += Di * Aq[(i * m.NA + lane) * 24 + k];
+        }
+    }
     // every group of the wave takes the same number of turns, so that the shuffles meet whole waves
     int turns = n;
 #pragma unroll
@@ -422,12 +428,11 @@ __global__ __launch_bounds__(64) void k_nep_pair(const int *__restrict__ verlet,
     }
 }
 
-constexpr int NEP_GATHER_W = 8;
-
-template <bool TRI>
+// ADD: the force and the virial start from addf, addv (a charge model's electrostatic part) instead of zero
+template <bool TRI, bool ADD>
 __global__ __launch_bounds__(64) void k_nep_gather(const int *__restrict__ verlet, const int *__restrict__ nn, int64_t N, int64_t M, DBox b,
                                                    const Pos4 *__restrict__ rec, const double *__restrict__ table, double *__restrict__ force,
-                                                   double *__restrict__ virial)
+                                                   double *__restrict__ virial, const double *__restrict__ addf, const double *__restrict__ addv)
 {
     constexpr int W = NEP_GATHER_W, G = 64 / W;
     const int lane = threadIdx.x % W, grp = threadIdx.x / W;
@@ -447,11 +452,7 @@ __global__ __launch_bounds__(64) void k_nep_gather(const int *__restrict__ verle
         double d[3] = {rj.x - ri.x, rj.y - ri.y, rj.z - ri.z};
         nep_image<TRI>(b, d[0], d[1], d[2]);
         // where row j names i: its pair force on the way back
-        const int nj = min(max(nn[j], 0), (int)M);
-        const int *row = verlet + (int64_t)j * M;
-        int back = -1;
-        for (int q = 0; q < nj; ++q)
-            if (row[q] == (int)i) { back = q; break; }
+        const int back = nep_back(verlet, nn, M, j, i);
         const double *mine = table + (i * M + slot) * 3;
         double other[3] = {0.0, 0.0, 0.0};
         if (back >= 0) {
@@ -473,12 +474,137 @@ __global__ __launch_bounds__(64) void k_nep_gather(const int *__restrict__ verle
         return;
     if (force) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) force[3 * i + a] = f[a];
+        for (int a = 0; a < 3; ++a) force[3 * i + a] = ADD ? addf[3 * i + a] + f[a] : f[a];
     }
     if (virial) {
 #pragma unroll
-        for (int a = 0; a < 9; ++a) virial[9 * i + a] = v[a];
+        for (int a = 0; a < 9; ++a) virial[9 * i + a] = ADD ? addv[9 * i + a] + v[a] : v[a];
     }
+}
+
+// ---------------------------------------------------------------------------------------------- host side, shared by the two entries (nep_core.hpp declares it)
+// the header words -> the model's shape and the offsets into its block (m.p is left alone); len: the block's length.
+// charge: the entry reads a charge model (w1 of 2 x neurons per type, sqrt(epsilon_inf) before the common bias).
+// -> MDH_OK, or MDH_ERR_ARG with the error set
+int nep_model_of(const std::string &who, const int *h, int nfile, const double *zbl3_host, const int *type_map_host, bool charge,
+                        NepModel &m, int64_t &len)
+{
+    m.T = h[0]; m.NR = h[1]; m.KR = h[2]; m.NA = h[3]; m.KA = h[4]; m.L3 = h[5]; m.L4 = h[6]; m.L5 = h[7]; m.H = h[8]; m.mode = h[9];
+    m.nfile = nfile;
+    m.charge = charge ? h[11] : 0;
+    if (m.L3 < 1 || m.L3 > 4 || (m.L4 != 0 && m.L4 != 2) || (m.L5 != 0 && m.L5 != 1) || (m.L4 == 2 && m.L3 < 2)) {
+        set_error(who + ": l_max out of scope (3-body 1..4, 4-body 0 or 2, 5-body 0 or 1)");
+        return MDH_ERR_ARG;
+    }
+    if (m.T < 1 || m.T > NEP_MAX_FILE_TYPES || nfile < 1 || nfile > NEP_MAX_FILE_TYPES || m.NR < 1 || m.NR > NEP_MAX_N || m.NA < 1 ||
+        m.NA > NEP_MAX_N || m.KR < 1 || m.KR > NEP_MAX_K || m.KA < 1 || m.KA > NEP_MAX_K || m.H < 1 || m.H > NEP_MAX_NEURON || m.mode < 0 ||
+        m.mode > 2) {
+        set_error(who + ": the model is larger than the compiled maxima (96 types, n_max 15, basis_size 16, 128 neurons, descriptor dimension 112)");
+        return MDH_ERR_ARG;
+    }
+    if (charge && (m.charge < 1 || m.charge > 3)) {
+        set_error(who + ": charge mode outside 1..3");
+        return MDH_ERR_ARG;
+    }
+    m.dim = m.NR + m.NA * (m.L3 + (m.L4 == 2) + (m.L5 == 1));
+    int64_t at = 0;
+    m.o_rc_r = (int)at; at += m.T;
+    m.o_rc_a = (int)at; at += m.T;
+    m.o_z = (int)at; at += m.T;
+    m.o_rcov = (int)at; at += m.T;
+    m.o_scaler = (int)at; at += m.dim;
+    m.o_cr = (int)at; at += (int64_t)m.T * m.T * m.NR * m.KR;
+    m.o_ca = (int)at; at += (int64_t)m.T * m.T * m.NA * m.KA;
+    m.o_net = (int)at;
+    m.net_stride = m.H * (m.dim + (charge ? 3 : 2)) + 1;
+    at += (int64_t)m.T * m.net_stride;
+    m.o_eps = (int)at; at += charge ? 1 : 0;
+    m.o_b1 = (int)at; at += 1;
+    len = at;
+    if (at != (int64_t)h[10]) { set_error(who + ": the model block's length does not belong to its header"); return MDH_ERR_ARG; }
+    m.zbl_inner = zbl3_host[0]; m.zbl_outer = zbl3_host[1]; m.zbl_factor = zbl3_host[2];
+    if (m.mode && !(m.zbl_outer > 0.0 && m.zbl_inner >= 0.0 && m.zbl_inner < m.zbl_outer)) {
+        set_error(who + ": ZBL needs 0 <= inner < outer");
+        return MDH_ERR_ARG;
+    }
+    for (int t = 0; t < nfile; ++t)
+        if (type_map_host[t] < -1 || type_map_host[t] >= m.T) { set_error(who + ": a type map entry outside [-1, T)"); return MDH_ERR_ARG; }
+    return MDH_OK;
+}
+
+void nep_launch_pack(hipStream_t st, const double *x, const double *y, const double *z, const int *type, const NepTypeMap &map, int64_t N,
+                     const NepModel &m, Pos4 *rec)
+{
+    hipLaunchKernelGGL(k_nep_pack, dim3(grid_for(N, 256)), dim3(256), 0, st, x, y, z, type, map, m.nfile, m.T, N, rec);
+}
+
+template <bool Q>
+static void launch_descriptor(hipStream_t st, const NepPassArgs &a, double *energy, double *FpR, double *A, double *descriptor, double *latent,
+                              double *charge, double *FpRq, double *Aq)
+{
+    auto launch = [&](auto kernel, int atoms) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(a.N, atoms)), dim3(64), 0, st, a.verlet, a.dist, a.nn, a.N, a.M, a.b, a.rec, a.m, energy, FpR, A,
+                           descriptor, latent, charge, FpRq, Aq);
+    };
+    if (a.wide())
+        a.b.tri ? launch(k_nep_descriptor<16, true, Q>, 4) : launch(k_nep_descriptor<16, false, Q>, 4);
+    else
+        a.b.tri ? launch(k_nep_descriptor<8, true, Q>, 8) : launch(k_nep_descriptor<8, false, Q>, 8);
+}
+
+void nep_launch_descriptor(hipStream_t st, const NepPassArgs &a, double *energy, double *FpR, double *A, double *descriptor, double *latent,
+                           double *charge, double *FpRq, double *Aq)
+{
+    ProfRange pr("k_nep_descriptor", st);
+    if (charge)
+        launch_descriptor<true>(st, a, energy, FpR, A, descriptor, latent, charge, FpRq, Aq);
+    else
+        launch_descriptor<false>(st, a, energy, FpR, A, descriptor, latent, nullptr, nullptr, nullptr);
+}
+
+template <bool Q>
+static void launch_pair(hipStream_t st, const NepPassArgs &a, const double *FpR, const double *A, double *table, const double *FpRq,
+                        const double *Aq, const double *D)
+{
+    auto launch = [&](auto kernel, int atoms) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(a.N, atoms)), dim3(64), 0, st, a.verlet, a.dist, a.nn, a.N, a.M, a.b, a.rec, a.m, FpR, A, table,
+                           FpRq, Aq, D);
+    };
+    if (a.wide())
+        a.b.tri ? launch(k_nep_pair<16, true, Q>, 4) : launch(k_nep_pair<16, false, Q>, 4);
+    else
+        a.b.tri ? launch(k_nep_pair<8, true, Q>, 8) : launch(k_nep_pair<8, false, Q>, 8);
+}
+
+void nep_launch_pair(hipStream_t st, const NepPassArgs &a, const double *FpR, const double *A, double *table, const double *FpRq, const double *Aq,
+                     const double *D)
+{
+    ProfRange pr("k_nep_pair", st);
+    if (D)
+        launch_pair<true>(st, a, FpR, A, table, FpRq, Aq, D);
+    else
+        launch_pair<false>(st, a, FpR, A, table, nullptr, nullptr, nullptr);
+}
+
+template <bool ADD>
+static void launch_gather(hipStream_t st, const NepPassArgs &a, const double *table, double *force, double *virial, const double *addf,
+                          const double *addv)
+{
+    const dim3 grid(grid_for(a.N, 64 / NEP_GATHER_W));
+    if (a.b.tri)
+        hipLaunchKernelGGL((k_nep_gather<true, ADD>), grid, dim3(64), 0, st, a.verlet, a.nn, a.N, a.M, a.b, a.rec, table, force, virial, addf, addv);
+    else
+        hipLaunchKernelGGL((k_nep_gather<false, ADD>), grid, dim3(64), 0, st, a.verlet, a.nn, a.N, a.M, a.b, a.rec, table, force, virial, addf, addv);
+}
+
+void nep_launch_gather(hipStream_t st, const NepPassArgs &a, const double *table, double *force, double *virial, const double *addf,
+                       const double *addv)
+{
+    ProfRange pr("k_nep_gather", st);
+    if (addf)
+        launch_gather<true>(st, a, table, force, virial, addf, addv);
+    else
+        launch_gather<false>(st, a, table, force, virial, nullptr, nullptr);
 }
 
 } // namespace mdh
@@ -497,40 +623,8 @@ int mdh_nep(const double *x, const double *y, const double *z, const int *type, 
     if (n_real < 0 || n_real > N) { set_error("mdh_nep: n_real outside [0, N]"); return MDH_ERR_ARG; }
     if (virial_sum9 && !virial) { set_error("mdh_nep: virial_sum9 needs virial"); return MDH_ERR_ARG; }
     NepModel m;
-    const int *h = head12_host;
-    m.T = h[0]; m.NR = h[1]; m.KR = h[2]; m.NA = h[3]; m.KA = h[4]; m.L3 = h[5]; m.L4 = h[6]; m.L5 = h[7]; m.H = h[8]; m.mode = h[9];
-    m.nfile = nfile;
-    if (m.L3 < 1 || m.L3 > 4 || (m.L4 != 0 && m.L4 != 2) || (m.L5 != 0 && m.L5 != 1) || (m.L4 == 2 && m.L3 < 2)) {
-        set_error("mdh_nep: l_max out of scope (3-body 1..4, 4-body 0 or 2, 5-body 0 or 1)");
-        return MDH_ERR_ARG;
-    }
-    if (m.T < 1 || m.T > NEP_MAX_FILE_TYPES || nfile < 1 || nfile > NEP_MAX_FILE_TYPES || m.NR < 1 || m.NR > NEP_MAX_N || m.NA < 1 ||
-        m.NA > NEP_MAX_N || m.KR < 1 || m.KR > NEP_MAX_K || m.KA < 1 || m.KA > NEP_MAX_K || m.H < 1 || m.H > NEP_MAX_NEURON || m.mode < 0 ||
-        m.mode > 2) {
-        set_error("mdh_nep: the model is larger than the compiled maxima (96 types, n_max 15, basis_size 16, 128 neurons, descriptor dimension 112)");
-        return MDH_ERR_ARG;
-    }
-    m.dim = m.NR + m.NA * (m.L3 + (m.L4 == 2) + (m.L5 == 1));
     int64_t at = 0;
-    m.o_rc_r = (int)at; at += m.T;
-    m.o_rc_a = (int)at; at += m.T;
-    m.o_z = (int)at; at += m.T;
-    m.o_rcov = (int)at; at += m.T;
-    m.o_scaler = (int)at; at += m.dim;
-    m.o_cr = (int)at; at += (int64_t)m.T * m.T * m.NR * m.KR;
-    m.o_ca = (int)at; at += (int64_t)m.T * m.T * m.NA * m.KA;
-    m.o_net = (int)at;
-    m.net_stride = m.H * (m.dim + 2) + 1;
-    at += (int64_t)m.T * m.net_stride;
-    m.o_b1 = (int)at; at += 1;
-    if (at != (int64_t)h[10]) { set_error("mdh_nep: the model block's length does not belong to its header"); return MDH_ERR_ARG; }
-    m.zbl_inner = zbl3_host[0]; m.zbl_outer = zbl3_host[1]; m.zbl_factor = zbl3_host[2];
-    if (m.mode && !(m.zbl_outer > 0.0 && m.zbl_inner >= 0.0 && m.zbl_inner < m.zbl_outer)) {
-        set_error("mdh_nep: ZBL needs 0 <= inner < outer");
-        return MDH_ERR_ARG;
-    }
-    for (int t = 0; t < nfile; ++t)
-        if (type_map_host[t] < -1 || type_map_host[t] >= m.T) { set_error("mdh_nep: a type map entry outside [-1, T)"); return MDH_ERR_ARG; }
+    MDH_TRY(nep_model_of("mdh_nep", head12_host, nfile, zbl3_host, type_map_host, false, m, at));
     if (space == MDH_HOST && type)
         for (int64_t i = 0; i < N; ++i)
             if (type[i] < 0 || type[i] >= nfile) { set_error("mdh_nep: an atom's type outside the type map"); return MDH_ERR_ARG; }
@@ -569,37 +663,12 @@ int mdh_nep(const double *x, const double *y, const double *z, const int *type, 
     if (!rec || (pairs && (!FpR || !A || !table)))
         return sc.error();
     hipStream_t st = sc.stream();
-    hipLaunchKernelGGL(k_nep_pack, dim3(grid_for(N, 256)), dim3(256), 0, st, dx, dy, dz, dt, dmap, nfile, m.T, N, rec);
-    const bool wide = std::max(m.NR, m.NA) > 8;
-    {
-        ProfRange pr("k_nep_descriptor", st);
-        auto launch = [&](auto kernel, int atoms) {
-            hipLaunchKernelGGL(kernel, dim3(grid_for(N, atoms)), dim3(64), 0, st, dv, dd, dn, N, M, b, rec, m, de, FpR, A, dq, dl);
-        };
-        if (wide)
-            b.tri ? launch(k_nep_descriptor<16, true>, 4) : launch(k_nep_descriptor<16, false>, 4);
-        else
-            b.tri ? launch(k_nep_descriptor<8, true>, 8) : launch(k_nep_descriptor<8, false>, 8);
-    }
+    nep_launch_pack(st, dx, dy, dz, dt, dmap, N, m, rec);
+    const NepPassArgs pass{dv, dd, dn, N, M, b, rec, m};
+    nep_launch_descriptor(st, pass, de, FpR, A, dq, dl, nullptr, nullptr, nullptr);
     if (pairs) {
-        {
-            ProfRange pr("k_nep_pair", st);
-            auto launch = [&](auto kernel, int atoms) {
-                hipLaunchKernelGGL(kernel, dim3(grid_for(N, atoms)), dim3(64), 0, st, dv, dd, dn, N, M, b, rec, m, FpR, A, table);
-            };
-            if (wide)
-                b.tri ? launch(k_nep_pair<16, true>, 4) : launch(k_nep_pair<16, false>, 4);
-            else
-                b.tri ? launch(k_nep_pair<8, true>, 8) : launch(k_nep_pair<8, false>, 8);
-        }
-        {
-            ProfRange pr("k_nep_gather", st);
-            const dim3 grid(grid_for(N, 64 / NEP_GATHER_W));
-            if (b.tri)
-                hipLaunchKernelGGL(k_nep_gather<true>, grid, dim3(64), 0, st, dv, dn, N, M, b, rec, table, df, dw);
-            else
-                hipLaunchKernelGGL(k_nep_gather<false>, grid, dim3(64), 0, st, dv, dn, N, M, b, rec, table, df, dw);
-        }
+        nep_launch_pair(st, pass, FpR, A, table, nullptr, nullptr, nullptr);
+        nep_launch_gather(st, pass, table, df, dw, nullptr, nullptr);
         if (dsum) {
             launch_virial_sum(sc, dw, n_real, dsum);
             if (sc.failed())

@@ -45,8 +45,9 @@ def resources():
         if not m:
             continue
         if m.group(1) == "Function Name":
-            width, tri = re.search(r"ILi(\d+)E", m.group(2)), re.search(r"Lb([01])E", m.group(2))
-            marks = ([width.group(1)] if width else []) + (["tri" if tri.group(1) == "1" else "ortho"] if tri else [])
+            width, flags = re.search(r"ILi(\d+)E", m.group(2)), re.findall(r"Lb([01])E", m.group(2))
+            marks = ([width.group(1)] if width else []) + (["tri" if flags[0] == "1" else "ortho"] if flags else [])
+            marks += ["charge"] if len(flags) > 1 and flags[1] == "1" else []  # (the instantiations csrc/nep_charge.hip launches)
             name = re.sub(r"^_ZN3mdh\d+(k_\w+?)(I|E).*$", r"\1", m.group(2)) + (f"<{', '.join(marks)}>" if marks else "")
             table[name] = {}
         elif name and m.group(1) in keys:
